@@ -9,6 +9,13 @@ scenes (aec_amd.synth), seed-0 reference weights, inputs resident in HBM.
 N>1 (torchrun): every rank runs its own 256 streams (weak scaling, no data-path
 collective); timing = max over ranks.
 
+A plain run sets up, warms up, times --steps steps and prints the headline
+figures.  --full adds every other figure of the line (per-kernel times and
+rooflines, the near=None leg, RTF at batch 1, the batch sweep, C3 / C4 / C5,
+the training step, the CPU baselines, the ERLE checks); their keys are null
+in a plain run's line.  --dump-outputs DIR writes the last timed step's
+outputs as DIR/<name>.npy.
+
 Prints ONE JSON line (rank 0).
 """
 from __future__ import annotations
@@ -114,7 +121,44 @@ def parse():
     ap.add_argument('--no-near-leg', action='store_true',
                     help='skip the near=None (no loss) timed leg reported beside the headline')
     ap.add_argument('--train-steps', type=int, default=10, help='timed steps of the training-step figure')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beside the headline: per-kernel / per-stage times and rooflines, '
+                         'the near=None leg, RTF at batch 1, the batch sweep, C3 / C4 / C5, the training step, the '
+                         'CPU baselines and the ERLE checks (each still has its own --no-* switch).  Without it '
+                         'the run sets up, warms up, times --steps steps and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step returned (out_wav, and loss where '
+                         'the path computes one) as DIR/<name>.npy, float32; see dump_outputs()')
+    args = ap.parse_args()
+    if not args.full:
+        args.no_cpu = args.no_rtf = args.no_sweep = args.no_c3 = args.no_train = args.no_near_leg = True
+    return args
+
+
+DUMP_BYTES = 48 << 20         # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(dirname, arrays):
+    """Write each tensor of `arrays` (name -> what the last timed step returned)
+    as dirname/<name>.npy in float32.  A tensor that does not fit in what is
+    left of DUMP_BYTES is cut to a fixed choice of its rows (numpy
+    default_rng(0), sorted), which depends on its shape alone, so two runs
+    with the same arguments write the same rows."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    left = DUMP_BYTES
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        t = t.detach().float()
+        row_bytes = max(1, t[0].numel() * 4) if t.dim() > 1 else 4
+        if t.numel() * 4 > left:
+            keep = max(1, left // row_bytes)
+            rows = np.sort(np.random.default_rng(0).choice(t.shape[0], size=keep, replace=False))
+            t = t[rows.tolist()]
+        a = t.cpu().numpy()
+        left -= a.nbytes
+        np.save(os.path.join(dirname, name + '.npy'), a)
 
 
 # knobs that only an A/B build reads (csrc/aec_knobs.h AEC_AB_KNOB): timing experiments and
@@ -358,11 +402,12 @@ def _init_dist(torch, dist, world, local):
     return local
 
 
-def run_crn(args, dev, rank, world, dtype, steps, warmup, B, n, with_cpu, nlms=None, with_erle=None):
+def run_crn(args, dev, rank, world, dtype, steps, warmup, B, n, with_cpu, nlms=None, with_erle=None, dump=None):
     """BASELINE config 3: the DCCRN post-filter (dccrn2.py, configs.net_conf) on
     B streams x n samples; returns the measurements (timing = max over ranks).
     nlms: the FD-NLMS front end (C5: NLMS -> CRN, include/aec_crn.h), timed
-    in the 'front' stage."""
+    in the 'front' stage.  The stage times and the rooflines priced from them
+    take a sequential pass of their own (--full).  dump: --dump-outputs' directory."""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -397,27 +442,32 @@ def run_crn(args, dev, rank, world, dtype, steps, warmup, B, n, with_cpu, nlms=N
         for _ in range(max(warmup, inflight)):
             step()
         torch.cuda.synchronize(dev)
-        # stage times: HIP events over a sequential pass (one batch in flight)
-        h = net._handle(dev)
-        prof_steps = max(1, min(steps, 5))
-        h.profile_enable(True)
-        h.profile_read()
-        for _ in range(prof_steps):
-            net.forward_ragged(mic, far, lens, want_spec=False)
-        torch.cuda.synchronize(dev)
-        sms, calls = h.profile_read()
-        h.profile_enable(False)
+        sms, calls = None, 0
+        if args.full:
+            # stage times: HIP events over a sequential pass (one batch in flight)
+            h = net._handle(dev)
+            prof_steps = max(1, min(steps, 5))
+            h.profile_enable(True)
+            h.profile_read()
+            for _ in range(prof_steps):
+                net.forward_ragged(mic, far, lens, want_spec=False)
+            torch.cuda.synchronize(dev)
+            sms, calls = h.profile_read()
+            h.profile_enable(False)
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
         for _ in range(steps):
-            step()
+            last = step()
         torch.cuda.synchronize(dev)
         if world > 1:
             dist.barrier()
         el = time.perf_counter() - t0
         el = shard.max_over_ranks(el)
+        if dump and rank == 0:
+            dump_outputs(dump, {'out_wav': last[0]})
+        del last
         lat = []
         for _ in range(0 if args.no_rtf else 3):
             torch.cuda.synchronize(dev)
@@ -428,11 +478,21 @@ def run_crn(args, dev, rank, world, dtype, steps, warmup, B, n, with_cpu, nlms=N
         rtf1 = float(np.median(lat)) / (n / 16000) if lat else None
     value = world * B * T * steps / el
     ms_step = el / steps * 1e3
-    stage_ms = {k: sms[i] / max(calls, 1) for i, k in enumerate(CRN_STAGES)}
     fl = crn_flops_per_frame(conf, args.crn_version)
+    whole = fl['total'] * B * T / (ms_step * 1e-3) / 1e12
     # fp8 runs only the LSTM input projections on the scaled fp8 MFMA; everything else is bf16,
     # so it is priced against the bf16 peak (conservative for the input-GEMM half of the LSTM stage)
     peak = FP32_PEAK_TFLOPS if dtype == 'f32' else BF16_PEAK_TFLOPS
+    res = dict(value=round(value, 1), value_per_gpu=round(value / world, 1), ms_per_step=round(ms_step, 3),
+               batches_in_flight=inflight, rtf_batch1=rtf1, stage_ms_per_step=None, roofline=None,
+               pipeline_roofline={'alg_flops_per_frame': fl['total'], 'achieved_tflops': round(whole, 1),
+                                  'mfma_frac': round(whole / peak, 4)},
+               erle=None, cpu_baseline=None)
+    if sms is None:
+        del net, nets
+        torch.cuda.empty_cache()
+        return res
+    stage_ms = {k: sms[i] / max(calls, 1) for i, k in enumerate(CRN_STAGES)}
     dom = max(stage_ms, key=stage_ms.get)
     dom_fl = fl.get(dom, 0)
     ach = dom_fl * B * T / (stage_ms[dom] * 1e-3) / 1e12 if dom_fl else 0.0
@@ -444,7 +504,6 @@ def run_crn(args, dev, rank, world, dtype, steps, warmup, B, n, with_cpu, nlms=N
         dom_peak = round(dom_fl / t_pk, 1)
         peak_note = ('blended: input-projection half (MX-fp8) at %.0f TF/s, recurrence half (bf16) at %.0f TF/s'
                      % (FP8_PEAK_TFLOPS, BF16_PEAK_TFLOPS))
-    whole = fl['total'] * B * T / (ms_step * 1e-3) / 1e12
     # HBM bytes of the LSTM stage per batch from the committed PMC passes
     # (profiles/pmc_latest_crn.json, tools/crn_pmc.sh + tools/crn_pmc_latest.py), same shape and dtype only
     traffic = None
@@ -453,16 +512,11 @@ def run_crn(args, dev, rank, world, dtype, steps, warmup, B, n, with_cpu, nlms=N
         pj = json.load(open(pp))
         if pj.get('dtype') == dtype and pj.get('B') == B and pj.get('N') == n:
             traffic = pj.get('lstm_stage_hbm_bytes_per_batch')
-    res = dict(value=round(value, 1), value_per_gpu=round(value / world, 1), ms_per_step=round(ms_step, 3),
-               batches_in_flight=inflight,
-               rtf_batch1=rtf1, stage_ms_per_step={k: round(v, 3) for k, v in stage_ms.items()},
+    res.update(stage_ms_per_step={k: round(v, 3) for k, v in stage_ms.items()},
                roofline={'bound': 'mfma', 'achieved': round(ach, 1), 'peak': dom_peak, 'unit': 'TFLOP/s',
                          'frac': round(ach / dom_peak, 4), 'traffic': traffic, 'peak_note': peak_note,
                          'kernel': f'{dom} stage ({"input GEMM + per-frame recurrence steps + combine per layer" if dom == "lstm" else "GEMM launches"})',
-                         'alg_flops_per_frame': dom_fl, 'frames_per_launch': B * T},
-               pipeline_roofline={'alg_flops_per_frame': fl['total'], 'achieved_tflops': round(whole, 1),
-                                  'mfma_frac': round(whole / peak, 4)},
-               erle=None, cpu_baseline=None)
+                         'alg_flops_per_frame': dom_fl, 'frames_per_launch': B * T})
     if with_erle and rank == 0 and world == 1:
         if with_cpu:
             res['cpu_baseline'] = cpu_baseline_crn(args.cpu_seconds, conf, args.crn_version, n=n, nlms=nlms)
@@ -826,7 +880,8 @@ def main_crn(args):
     import aec_amd
     prov = knob_provenance()
     nl = aec_amd.nlms_conf if args.crn_nlms else None
-    r = run_crn(args, dev, rank, world, args.crn_dtype, args.steps, args.warmup, B, n, not args.no_cpu, nl)
+    r = run_crn(args, dev, rank, world, args.crn_dtype, args.steps, args.warmup, B, n, not args.no_cpu, nl,
+                dump=args.dump_outputs)
     if rank == 0:
         line = {
             'metric': '16kHz frames/sec/GPU (batched AEC) + RTF@batch=1; ERLE delta vs reference',
@@ -842,6 +897,7 @@ def main_crn(args):
             'aggregate_frames_per_s': r['value'],
             'value_semantics': VALUE_SEMANTICS,
             'xRT': round(r['value'] * 256 / 16000, 1),
+            'full': args.full,
         }
         line.update({k: r[k] for k in ('rtf_batch1', 'stage_ms_per_step', 'roofline', 'pipeline_roofline',
                                        'erle', 'cpu_baseline')})
@@ -919,21 +975,23 @@ def main():
             return nets[k].forward_ragged(mic, ref, nr, erb, lens, lookahead=tokens.pop(n_, None))
 
     with torch.no_grad():
-        for _ in range(2):
-            nets[0].forward_ragged(mic, ref, near, erb, lens)
-        torch.cuda.synchronize(dev)
-        # per-kernel times (roofline): HIP events around each kernel over a
-        # sequential pass (one batch in flight, so no event interval contains
-        # another batch's kernels; no look-ahead, so the moments pass is inside)
-        h0 = nets[0]._handle(dev)[0]
-        prof_steps = max(1, min(args.steps, 10))
-        h0.profile_enable(True)
-        torch.cuda.synchronize(dev)
-        for _ in range(prof_steps):
-            nets[0].forward_ragged(mic, ref, near, erb, lens)
-        torch.cuda.synchronize(dev)
-        kms, calls = h0.profile_read()
-        h0.profile_enable(False)
+        kms = None
+        if args.full:
+            for _ in range(2):
+                nets[0].forward_ragged(mic, ref, near, erb, lens)
+            torch.cuda.synchronize(dev)
+            # per-kernel times (roofline): HIP events around each kernel over a
+            # sequential pass (one batch in flight, so no event interval contains
+            # another batch's kernels; no look-ahead, so the moments pass is inside)
+            h0 = nets[0]._handle(dev)[0]
+            prof_steps = max(1, min(args.steps, 10))
+            h0.profile_enable(True)
+            torch.cuda.synchronize(dev)
+            for _ in range(prof_steps):
+                nets[0].forward_ragged(mic, ref, near, erb, lens)
+            torch.cuda.synchronize(dev)
+            kms, calls = h0.profile_read()
+            h0.profile_enable(False)
         # warm-up steps in the timed loop's own form (the last one queues the first timed batch's
         # look-ahead pass): at least MIN_WARM_STEPS of them (~20 ms of continuous load).  The chip
         # clocks up over its first ~20 ms under this load: after 5 warm-up steps the first ~20
@@ -949,12 +1007,15 @@ def main():
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            step()
+            last = step()
         torch.cuda.synchronize(dev)
         if world > 1:
             dist.barrier()
         el = time.perf_counter() - t0
         el = shard.max_over_ranks(el)              # all_reduce(MAX) of one scalar, outside the timed region
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {'loss': last[1], 'out_wav': last[0]})
+        del last
         # the same pipelined step without the near-end signal (reported beside `value`, never as it):
         # the enhanced waveform only, as the reference's inference entry point uses it (test.py:157
         # keeps out_wav and discards the loss); the look-ahead queue is drained and refilled first,
@@ -1020,41 +1081,45 @@ def main():
     frames_total = world * B * T * args.steps
     value = frames_total / el
     ms_step = el / args.steps * 1e3
-    # `calls` counts aec_process calls (profile marks per call; one launch of each
-    # kernel per call here: 256 streams, no sub-batching)
-    calls_per_step = max(calls, 1) / prof_steps
-    per_kernel_ms = {k: kms[i] / prof_steps for i, k in enumerate(KERNELS)}
-    per_launch_ms = {k: kms[i] / max(calls, 1) for i, k in enumerate(KERNELS)}
     if args.pipeline == 'full' and os.environ.get('AEC_FUSED_SYNTH', '1') != '0':
-        # one fused launch: its time is in the 'gru' slot, the 'synthesis' slot is an empty interval
         kernels_per_call = ['moments_lds_kernel', 'norm_finalize_kernel', 'nlms_analysis_kernel', 'gru_synth_kernel']
-        for d in (per_kernel_ms, per_launch_ms):
-            d['gru_synthesis'] = d.pop('gru') + d.pop('synthesis')
     else:
         kernels_per_call = ['moments_lds_kernel', 'norm_finalize_kernel', 'analysis_kernel', 'gru_kernel',
                             'synthesis_kernel']
-    launches_per_step = calls_per_step * len(kernels_per_call)
-    dom = max(per_kernel_ms, key=per_kernel_ms.get)
-    pmc = None
-    pmc_path = os.path.join(REPO, 'profiles', f'pmc_latest_{args.pipeline}.json')
-    if os.path.exists(pmc_path):
-        pmc = json.load(open(pmc_path))
-    roof = roofline(args.pipeline, dom, per_launch_ms[dom], int(round(B * T / calls_per_step)), pmc)
-    if args.pipeline == 'full':
-        roof['sq'] = sq_limiter(dom)
-        roof['limiter'] = roof['sq']['limiter'] if roof['sq'] else None
-    # every kernel of the step against its own roofline (the fused GRU + synthesis kernel runs two
-    # streams per block on half the CUs, so the longest launch is not the one holding the most CU
-    # time): the same figures as `roofline`, per kernel
-    kernel_rooflines = {}
-    for k in per_launch_ms:
-        if per_launch_ms[k] > 0 and k in ALG[args.pipeline]:
-            r = roofline(args.pipeline, k, per_launch_ms[k], int(round(B * T / calls_per_step)), pmc)
-            kernel_rooflines[k] = {x: r[x] for x in ('bound', 'frac', 'hbm_frac', 'fp32_frac', 'ms_per_launch',
-                                                     'traffic', 'traffic_alg_bytes_per_launch')}
-            # `bound` is the roofline the kernel's algorithmic work is priced against; `sq` says what
-            # the counters show limits it (C2's kernels: latency, not HBM or VALU throughput)
-            kernel_rooflines[k]['sq'] = sq_limiter(k) if args.pipeline == 'full' else None
+    # the per-kernel figures come from the profiled pass (--full)
+    per_kernel_ms = launches_per_step = roof = kernel_rooflines = None
+    if kms is not None:
+        # `calls` counts aec_process calls (profile marks per call; one launch of each
+        # kernel per call here: 256 streams, no sub-batching)
+        calls_per_step = max(calls, 1) / prof_steps
+        per_kernel_ms = {k: kms[i] / prof_steps for i, k in enumerate(KERNELS)}
+        per_launch_ms = {k: kms[i] / max(calls, 1) for i, k in enumerate(KERNELS)}
+        if len(kernels_per_call) == 4:
+            # one fused launch: its time is in the 'gru' slot, the 'synthesis' slot is an empty interval
+            for d in (per_kernel_ms, per_launch_ms):
+                d['gru_synthesis'] = d.pop('gru') + d.pop('synthesis')
+        launches_per_step = calls_per_step * len(kernels_per_call)
+        dom = max(per_kernel_ms, key=per_kernel_ms.get)
+        pmc = None
+        pmc_path = os.path.join(REPO, 'profiles', f'pmc_latest_{args.pipeline}.json')
+        if os.path.exists(pmc_path):
+            pmc = json.load(open(pmc_path))
+        roof = roofline(args.pipeline, dom, per_launch_ms[dom], int(round(B * T / calls_per_step)), pmc)
+        if args.pipeline == 'full':
+            roof['sq'] = sq_limiter(dom)
+            roof['limiter'] = roof['sq']['limiter'] if roof['sq'] else None
+        # every kernel of the step against its own roofline (the fused GRU + synthesis kernel runs two
+        # streams per block on half the CUs, so the longest launch is not the one holding the most CU
+        # time): the same figures as `roofline`, per kernel
+        kernel_rooflines = {}
+        for k in per_launch_ms:
+            if per_launch_ms[k] > 0 and k in ALG[args.pipeline]:
+                r = roofline(args.pipeline, k, per_launch_ms[k], int(round(B * T / calls_per_step)), pmc)
+                kernel_rooflines[k] = {x: r[x] for x in ('bound', 'frac', 'hbm_frac', 'fp32_frac', 'ms_per_launch',
+                                                         'traffic', 'traffic_alg_bytes_per_launch')}
+                # `bound` is the roofline the kernel's algorithmic work is priced against; `sq` says what
+                # the counters show limits it (C2's kernels: latency, not HBM or VALU throughput)
+                kernel_rooflines[k]['sq'] = sq_limiter(k) if args.pipeline == 'full' else None
     pipe_t = ms_step * 1e-3
     pipe_gbs = PIPE['bytes'] * B * T / pipe_t / 1e9
     pipe_tfl = path_flops(args.pipeline) * B * T / pipe_t / 1e12
@@ -1158,8 +1223,10 @@ def main():
             'value_semantics': VALUE_SEMANTICS,
             'xRT': round(value * 256 / 16000, 1),
             'rtf_batch1': rtf1,
-            'kernel_ms_per_step': {k: round(v, 4) for k, v in per_kernel_ms.items()},
-            'kernel_timing': f'HIP events around each kernel, sequential pass of {prof_steps} steps (1 batch in flight)',
+            'full': args.full,
+            'kernel_ms_per_step': {k: round(v, 4) for k, v in per_kernel_ms.items()} if per_kernel_ms else None,
+            'kernel_timing': f'HIP events around each kernel, sequential pass of {prof_steps} steps (1 batch in '
+                             'flight)' if per_kernel_ms else None,
             'kernels_per_step': kernels_per_call,
             'launches_per_step': launches_per_step,
             'roofline': roof,

@@ -162,3 +162,48 @@ def test_bench_refuses_timing_only_knobs(monkeypatch):
         with pytest.raises(SystemExit):
             bench.knob_provenance()
         monkeypatch.delenv(k)
+
+
+def test_bench_plain_run_is_lean_and_full_restores_every_leg(monkeypatch):
+    """Without --full every leg beside the timed steps is off (the line's
+    other figures are null); --full leaves each leg to its own --no-* switch."""
+    import importlib
+    sys.path.insert(0, REPO)
+    bench = importlib.import_module('bench')
+    legs = ('no_cpu', 'no_rtf', 'no_sweep', 'no_c3', 'no_train', 'no_near_leg')
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '7', '--warmup', '2'])
+    a = bench.parse()
+    assert not a.full and a.steps == 7 and a.warmup == 2 and a.dump_outputs is None
+    assert all(getattr(a, k) for k in legs)
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--no-train', '--dump-outputs', 'd'])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == 'd' and a.no_train
+    assert not any(getattr(a, k) for k in legs if k != 'no_train')
+
+
+def test_bench_dump_outputs_float32_bounded_and_repeatable(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy files, DUMP_BYTES at the most in all; an
+    array over the bound is cut to rows that depend on its shape alone."""
+    import importlib
+    import numpy as np
+    import torch
+    sys.path.insert(0, REPO)
+    bench = importlib.import_module('bench')
+    assert bench.DUMP_BYTES <= 64 * 10 ** 6
+    monkeypatch.setattr(bench, 'DUMP_BYTES', 4096)
+    g = torch.Generator().manual_seed(3)
+    out = torch.randn(37, 100, generator=g, dtype=torch.float64)
+    loss = torch.randn(37, generator=g)
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), {'loss': loss, 'out_wav': out, 'absent': None})
+    got = {f: np.load(tmp_path / 'a' / f) for f in sorted(os.listdir(tmp_path / 'a'))}
+    assert sorted(got) == ['loss.npy', 'out_wav.npy']
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert sum(v.nbytes for v in got.values()) <= 4096
+    assert np.array_equal(got['loss.npy'], loss.numpy())
+    rows = got['out_wav.npy']
+    assert rows.shape == ((4096 - 37 * 4) // 400, 100)
+    idx = [int(np.flatnonzero((out.float().numpy() == r).all(axis=1))[0]) for r in rows]
+    assert idx == sorted(set(idx))                       # distinct rows of the output, in order
+    for f, v in got.items():
+        assert np.array_equal(v, np.load(tmp_path / 'b' / f))

@@ -8,7 +8,7 @@ mkdir -p $O
 B="--no-cpu --no-c3 --no-rtf --no-sweep --no-train"
 for r in 1 2 3; do
   for n in 0 32 64 16 128; do
-    timeout -k 10 200 python $R/bench.py $B --lookahead-cus $n > $O/cus${n}_$r.log 2>&1 \
+    timeout -k 10 200 python $R/bench.py --full $B --lookahead-cus $n > $O/cus${n}_$r.log 2>&1 \
         || { echo "bench failed"; tail -20 $O/cus${n}_$r.log; exit 1; }
     echo "round $r lookahead_cus=$n: $(tail -1 $O/cus${n}_$r.log | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["ms_per_step"])')"
   done

@@ -11,7 +11,7 @@ for i in $(seq 1 $N); do
   for lib in "$@"; do
     tag=$(basename $lib .so)
     if [ "$lib" = tree ]; then unset AEC_HIP_LIB; else export AEC_HIP_LIB=$R/$lib; fi
-    timeout -k 10 150 python $R/bench.py --pipeline $PIPE --no-cpu --no-c3 --no-rtf --no-train --no-sweep --steps 40 \
+    timeout -k 10 150 python $R/bench.py --full --pipeline $PIPE --no-cpu --no-c3 --no-rtf --no-train --no-sweep --steps 40 \
         > $O/${tag}_$i.log 2>&1 || { tail -20 $O/${tag}_$i.log; exit 1; }
     echo "$tag #$i: $(grep '^{' $O/${tag}_$i.log | tail -1 | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["ms_per_step"], d.get("kernel_ms_per_step") or d.get("stage_ms_per_step"))')"
   done

@@ -3,11 +3,12 @@
 # post-filter-only bench, and rocprofv3 trace + PMC passes for both pipelines.
 set -uo pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}
+O=${OUT_DIR:-$R/bench_out}
 TAG=${1:-r01}
-mkdir -p $R/gpurun_out
-timeout -k 10 300 python $R/bench.py > $R/gpurun_out/bench_${TAG}_full.log 2>&1 || exit 1
+mkdir -p $O
+timeout -k 10 300 python $R/bench.py --full > $O/bench_${TAG}_full.log 2>&1 || exit 1
 echo "bench full done"
-timeout -k 10 300 python $R/bench.py --pipeline postfilter > $R/gpurun_out/bench_${TAG}_postfilter.log 2>&1 || exit 1
+timeout -k 10 300 python $R/bench.py --full --pipeline postfilter > $O/bench_${TAG}_postfilter.log 2>&1 || exit 1
 echo "bench postfilter done"
 # traces with one batch in flight: kernel durations without a concurrent batch,
 # the configuration of bench.py's own per-kernel timing pass
