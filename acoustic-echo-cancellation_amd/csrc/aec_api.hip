@@ -18,157 +18,9 @@
 
 #include "../../include/aec_hip.h"
 #include "aec_device.h"
+#include "aec_host.h"
 #include "aec_launch.h"
 #include "aec_tables.h"
-
-
-// ---------------------------------------------------------------------------
-// ERB tables (see aec_tables.h): balanced forward schedule + transpose table
-// ---------------------------------------------------------------------------
-namespace aec {
-ErbTables build_erb_tables(const float* erb) {
-    const int NB = 32, NF = 257, LANES = 16, SLOTS = 3;
-    ErbTables t;
-    std::vector<std::vector<int>> bins(NB);
-    int maxw = 0, nnz = 0;
-    for (int j = 0; j < NB; ++j) {
-        for (int k = 0; k < NF; ++k)
-            if (erb[k * NB + j] != 0.f) bins[j].push_back(k);
-        maxw = std::max(maxw, (int)bins[j].size());
-        nnz += (int)bins[j].size();
-    }
-    // transpose table: <= 2 bands per bin
-    t.bintab.assign(NF * 4, 0.f);
-    for (int k = 0; k < NF; ++k) {
-        int cnt = 0;
-        for (int j = 0; j < NB; ++j) {
-            const float v = erb[k * NB + j];
-            if (v == 0.f) continue;
-            if (cnt == 2) { t.why = "a bin lies in more than 2 bands"; return t; }
-            int ib = j;
-            std::memcpy(&t.bintab[k * 4 + 2 * cnt], &ib, 4);
-            t.bintab[k * 4 + 2 * cnt + 1] = v;
-            ++cnt;
-        }
-        if (cnt == 1) { int ib; std::memcpy(&ib, &t.bintab[k * 4], 4); std::memcpy(&t.bintab[k * 4 + 2], &ib, 4); }
-    }
-    // forward schedule: split bands wider than `split` in two, pack pieces
-    struct Piece { int band, first, count; };
-    for (int split = std::max(26, (maxw + 1) / 2); split <= NF; split += 2) {
-        std::vector<Piece> pieces;
-        for (int j = 0; j < NB; ++j) {
-            const int w = (int)bins[j].size();
-            if (w == 0) continue;
-            if (w > split) {
-                pieces.push_back({j, 0, (w + 1) / 2});
-                pieces.push_back({j, (w + 1) / 2, w - (w + 1) / 2});
-            } else {
-                pieces.push_back({j, 0, w});
-            }
-        }
-        std::stable_sort(pieces.begin(), pieces.end(), [](const Piece& a, const Piece& b) { return a.count > b.count; });
-        std::vector<std::vector<int>> lane(LANES);
-        std::vector<int> load(LANES, 0);
-        bool fits = true;
-        for (int p = 0; p < (int)pieces.size() && fits; ++p) {
-            int best = -1;
-            for (int l = 0; l < LANES; ++l)
-                if ((int)lane[l].size() < SLOTS && (best < 0 || load[l] < load[best])) best = l;
-            if (best < 0) fits = false;
-            else { lane[best].push_back(p); load[best] += pieces[p].count; }
-        }
-        if (!fits) continue;
-        int L = 0;
-        for (int l = 0; l < LANES; ++l) L = std::max(L, load[l]);
-        L = (L + 3) & ~3;
-        if (L > 48) { t.why = "ERB schedule longer than 48 entries per lane"; return t; }
-        t.sched_len = L;
-        t.sched.assign((size_t)L * LANES * 4 + 64, 0.f);
-        std::vector<int> comb(2 * NB, -1);
-        // Order every lane's entries so that at each step the 16 lanes read
-        // bins with distinct residues mod 16: with the per-frame XOR swizzle the
-        // 32 lanes of a ds_read_b32 then hit 32 distinct banks.  One bipartite
-        // matching (lanes x residues, Kuhn) per step; lanes with no slack left
-        // must take a real entry, the others may take a zero-weight padding
-        // entry on a free residue (bin = residue).
-        struct Item { int k, s; float w; };
-        std::vector<std::vector<Item>> items(LANES);
-        for (int l = 0; l < LANES; ++l)
-            for (int s = 0; s < (int)lane[l].size(); ++s) {
-                const Piece& pc = pieces[lane[l][s]];
-                for (int i = 0; i < pc.count; ++i) {
-                    const int k = bins[pc.band][pc.first + i];
-                    items[l].push_back({k, s, erb[k * NB + pc.band]});
-                }
-                const int slot = 3 * l + s;
-                if (comb[2 * pc.band] < 0) comb[2 * pc.band] = slot;
-                else comb[2 * pc.band + 1] = slot;
-            }
-        t.conflicts = 0;
-        for (int e = 0; e < L; ++e) {
-            const int left = L - e;
-            std::vector<int> owner(16, -1), match(LANES, -1);
-            std::vector<int> order(LANES);
-            for (int l = 0; l < LANES; ++l) order[l] = l;
-            std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-                return left - (int)items[a].size() < left - (int)items[b].size(); });
-            std::function<bool(int, std::vector<char>&)> aug = [&](int l, std::vector<char>& seen) -> bool {
-                for (const Item& it : items[l]) {
-                    const int r = it.k & 15;
-                    if (seen[r]) continue;
-                    seen[r] = 1;
-                    if (owner[r] < 0 || aug(owner[r], seen)) { owner[r] = l; match[l] = r; return true; }
-                }
-                return false;
-            };
-            for (int l : order) {
-                if (items[l].empty()) continue;
-                std::vector<char> seen(16, 0);
-                aug(l, seen);
-            }
-            for (int l = 0; l < LANES; ++l) {
-                float* en = &t.sched[((size_t)e * LANES + l) * 4];
-                if (match[l] >= 0) {
-                    for (size_t i = 0; i < items[l].size(); ++i)
-                        if ((items[l][i].k & 15) == match[l]) {
-                            const Item it = items[l][i];
-                            std::memcpy(&en[0], &it.k, 4);
-                            en[1 + it.s] = it.w;
-                            items[l].erase(items[l].begin() + i);
-                            break;
-                        }
-                } else if ((int)items[l].size() >= left) {       // no slack: take one anyway
-                    const Item it = items[l].front();
-                    std::memcpy(&en[0], &it.k, 4);
-                    en[1 + it.s] = it.w;
-                    items[l].erase(items[l].begin());
-                    ++t.conflicts;
-                } else {                                          // zero-weight padding on a free residue
-                    int r = 0;
-                    while (owner[r] >= 0) ++r;
-                    owner[r] = l;
-                    std::memcpy(&en[0], &r, 4);
-                }
-            }
-        }
-        // bands with no non-zeros read a zero slot: point both at a lane with < 3 pieces, else -1 pair
-        for (int j = 0; j < NB; ++j) {
-            if (comb[2 * j] < 0) {
-                int z = -1;
-                for (int l = 0; l < LANES && z < 0; ++l)
-                    if ((int)lane[l].size() < SLOTS) z = 3 * l + (int)lane[l].size();
-                if (z < 0) { t.why = "no zero slot for an empty band"; return t; }
-                comb[2 * j] = z;
-            }
-        }
-        std::memcpy(&t.sched[(size_t)L * LANES * 4], comb.data(), 64 * 4);
-        t.ok = true;
-        return t;
-    }
-    t.why = "could not balance the ERB schedule";
-    return t;
-}
-}  // namespace aec
 
 using namespace aec;
 
@@ -195,8 +47,8 @@ struct aec_handle {
     WorkItem* d_sitems = nullptr; // synthesis block-item list (15 hops)
     int64_t* d_len = nullptr;    // [B] mic length: sets the frame count and output length
     int32_t* d_slen = nullptr;   // [B][4] per-signal lengths (mic, ref, near, -): normaliser + zero padding
-    int64_t nitems = 0, nsitems = 0;
-    // look-ahead normaliser passes (aec_prepare_siglens), consumed in order by the process calls
+    // look-ahead normaliser passes (aec_prepare_siglens), consumed in order by the process calls:
+    // the device side of the two slots; `ring` (aec_host.h) records which are pending and for what
     struct PreSlot {
         double2* mom = nullptr;       // [cap][3][kMomChunks]
         float* cvals = nullptr;       // [cap][3]
@@ -207,15 +59,9 @@ struct aec_handle {
         hipEvent_t freed = nullptr;   // recorded after the consuming call's kernels
         bool used = false;            // done / freed recorded at least once
         bool freed_rec = false;
-        const float* sig[3] = {nullptr, nullptr, nullptr};
-        int64_t ld = 0;
-        int nsig = 0;
-        std::vector<int64_t> l3;
-        uint64_t token = 0;
     };
     PreSlot pre[2];
-    int pre_head = 0, pre_count = 0;
-    uint64_t next_token = 1;
+    PreRing ring;
     struct ListSlot {
         char* host = nullptr;    // pinned
         size_t cap = 0;
@@ -226,7 +72,7 @@ struct aec_handle {
     int slot_next = 0;
     int last_nsig = 0;
     int num_cus = 256;
-    std::vector<int64_t> item_off, sitem_off;   // first analysis / synthesis item of stream b (B+1 entries)
+    WorkLists lists;             // host copy of the last work lists (build_work_lists)
     // ordering of this handle's calls: a call on another stream than the last one
     // waits (on the device) for the last one, since they share the workspace
     hipEvent_t ev_last = nullptr;
@@ -237,7 +83,6 @@ struct aec_handle {
     float* d_dbg = nullptr;      // [2][B][T][32]  (h, mask)
     float2* d_spec = nullptr;    // [B][T][256] NLMS error spectrum (nlms_taps > 0 only)
     std::vector<int64_t> last_lens;                 // [B][3] of the last call (work lists rebuilt on change)
-    std::vector<WorkItem> h_items, h_sitems;        // host copies of the last work lists
     int debug = 0;
     int gru_mode = 0;            // AEC_GRU_MODE (A/B builds: timing experiments; results invalid unless 0)
     int nlms_mode = 0;           // AEC_NLMS_MODE: bit 4 two-pass ref ERB (tested); bits 0-3 A/B builds only (skip work)
@@ -325,6 +170,21 @@ static aec_status fail(aec_handle* h, aec_status s, const std::string& m) {
     return s;
 }
 
+// Growth of a buffer that only this handle's calls use: kernels of earlier calls may still read
+// the old one, so the host waits for the handle's last call (not the device), then frees and
+// allocates; `cap` is 0 while `p` is null.  `zero` clears the new buffer (synchronously).
+template <class T, class C>
+static aec_status grow_after_last(aec_handle* h, T*& p, C& cap, C new_cap, size_t bytes, bool zero = false) {
+    if (h->have_last) HIP_TRY(h, hipEventSynchronize(h->ev_last));
+    if (p) HIP_TRY(h, hipFree(p));
+    p = nullptr;
+    cap = 0;
+    HIP_TRY(h, hipMalloc(&p, bytes));
+    if (zero) HIP_TRY(h, hipMemset(p, 0, bytes));
+    cap = new_cap;
+    return AEC_OK;
+}
+
 namespace aec {
 // STFT constant tables, float64 math rounded to float32 (aec_tables.h)
 void build_dev_tables(DevTables& t) {
@@ -347,8 +207,8 @@ void build_dev_tables(DevTables& t) {
 extern "C" {
 
 size_t aec_weights_count(int32_t erb_bands) { return erb_bands == 32 ? kWeights32 : 0; }
-int64_t aec_num_frames(int64_t n) { return n / 256 + 1; }
-int64_t aec_out_len(int64_t n) { return 256 * (n / 256); }
+int64_t aec_num_frames(int64_t n) { return num_frames(n); }
+int64_t aec_out_len(int64_t n) { return out_len(n); }
 
 const char* aec_last_error(const aec_handle* h) { return h ? h->err.c_str() : "null handle"; }
 
@@ -476,48 +336,15 @@ static aec_status ensure_ws(aec_handle* h, int64_t B, int64_t T) {
 // first waits for the last one (begin_call).  The host waits only when it
 // reuses a staging slot whose copy (two list changes ago) is still in flight,
 // or when the device block must grow.
-static size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 static aec_status prepare_lists(aec_handle* h, const int64_t* lengths3, int32_t B, int nsig_in, hipStream_t st) {
     if (h->last_nsig == nsig_in && h->last_lens.size() == (size_t)B * 3 &&
         std::memcmp(h->last_lens.data(), lengths3, (size_t)B * 3 * sizeof(int64_t)) == 0)
         return AEC_OK;
-    std::vector<int64_t> lens(B);
-    for (int b = 0; b < B; ++b) lens[b] = lengths3[3 * b];
-    // analysis work list: 4-frame items of every stream, valid frames only
-    std::vector<WorkItem>& items = h->h_items;
-    items.clear();
-    h->item_off.assign(B + 1, 0);
-    for (int b = 0; b < B; ++b) {
-        h->item_off[b] = (int64_t)items.size();
-        const int64_t T = aec_num_frames(lens[b]);
-        for (int64_t wt = 0; wt < T; wt += 4) items.push_back({b, (int32_t)wt, lens[b]});
-    }
-    h->item_off[B] = (int64_t)items.size();
-    // synthesis work list: 15 output hops per block item
-    std::vector<WorkItem>& sitems = h->h_sitems;
-    sitems.clear();
-    h->sitem_off.assign(B + 1, 0);
-    for (int b = 0; b < B; ++b) {
-        h->sitem_off[b] = (int64_t)sitems.size();
-        const int64_t nhop = lens[b] / 256;
-        for (int64_t h0 = 0; h0 < nhop; h0 += kHopsOut) sitems.push_back({b, (int32_t)h0, lens[b]});
-    }
-    h->sitem_off[B] = (int64_t)sitems.size();
-    // block layout [items | sitems | len | slen], 16-B aligned pieces
-    const size_t o_si = align16(items.size() * sizeof(WorkItem));
-    const size_t o_len = o_si + align16(sitems.size() * sizeof(WorkItem));
-    const size_t o_slen = o_len + align16((size_t)B * sizeof(int64_t));
-    const size_t bytes = o_slen + align16((size_t)B * 4 * sizeof(int32_t));
+    WorkLists w = build_work_lists(lengths3, B);
+    const size_t bytes = w.bytes;
     if (bytes > h->lists_cap) {
-        // earlier kernels of this handle may read the old block: wait for the handle's last call
-        if (h->have_last) HIP_TRY(h, hipEventSynchronize(h->ev_last));
-        if (h->d_lists) HIP_TRY(h, hipFree(h->d_lists));
-        h->d_lists = nullptr;
-        h->lists_cap = 0;
-        const size_t cap = bytes + bytes / 4;
-        HIP_TRY(h, hipMalloc(&h->d_lists, cap));
-        h->lists_cap = cap;
+        const aec_status s = grow_after_last(h, h->d_lists, h->lists_cap, bytes + bytes / 4, bytes + bytes / 4);
+        if (s != AEC_OK) return s;
     }
     aec_handle::ListSlot& sl = h->slots[h->slot_next];
     h->slot_next ^= 1;
@@ -530,26 +357,46 @@ static aec_status prepare_lists(aec_handle* h, const int64_t* lengths3, int32_t 
         HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&sl.host), bytes + bytes / 4));
         sl.cap = bytes + bytes / 4;
     }
-    std::memcpy(sl.host, items.data(), items.size() * sizeof(WorkItem));
-    std::memcpy(sl.host + o_si, sitems.data(), sitems.size() * sizeof(WorkItem));
-    std::memcpy(sl.host + o_len, lens.data(), (size_t)B * sizeof(int64_t));
-    int32_t* slen = reinterpret_cast<int32_t*>(sl.host + o_slen);
-    for (int b = 0; b < B; ++b) {
-        for (int sg = 0; sg < 3; ++sg) slen[4 * b + sg] = (int32_t)(sg < nsig_in ? lengths3[3 * b + sg] : lens[b]);
-        slen[4 * b + 3] = 0;
-    }
+    std::memcpy(sl.host, w.items.data(), w.items.size() * sizeof(WorkItem));
+    std::memcpy(sl.host + w.o_si, w.sitems.data(), w.sitems.size() * sizeof(WorkItem));
+    int64_t* lens = reinterpret_cast<int64_t*>(sl.host + w.o_len);
+    for (int b = 0; b < B; ++b) lens[b] = lengths3[3 * b];
+    fill_slen(reinterpret_cast<int32_t*>(sl.host + w.o_slen), lengths3, B, nsig_in);
     HIP_TRY(h, hipMemcpyAsync(h->d_lists, sl.host, bytes, hipMemcpyHostToDevice, st));
     HIP_TRY(h, hipEventRecord(sl.ev, st));
     sl.pending = true;
     h->d_items = reinterpret_cast<WorkItem*>(h->d_lists);
-    h->d_sitems = reinterpret_cast<WorkItem*>(h->d_lists + o_si);
-    h->d_len = reinterpret_cast<int64_t*>(h->d_lists + o_len);
-    h->d_slen = reinterpret_cast<int32_t*>(h->d_lists + o_slen);
-    h->nitems = (int64_t)items.size();
-    h->nsitems = (int64_t)sitems.size();
+    h->d_sitems = reinterpret_cast<WorkItem*>(h->d_lists + w.o_si);
+    h->d_len = reinterpret_cast<int64_t*>(h->d_lists + w.o_len);
+    h->d_slen = reinterpret_cast<int32_t*>(h->d_lists + w.o_slen);
+    h->lists = std::move(w);
     h->last_lens.assign(lengths3, lengths3 + (size_t)B * 3);
     h->last_nsig = nsig_in;
     return AEC_OK;
+}
+
+// Argument blocks of the analysis and synthesis launches over the handle's work lists and tables:
+// what every call site shares (the caller sets mom / rows, spec / spec_stride / fmode).
+static AnalysisArgs analysis_args(const aec_handle* h, const float* mic, const float* ref, const float* near,
+                                  int64_t ld, int nsig, int64_t Tmax, const float* cvals) {
+    AnalysisArgs a{};
+    a.sig[0] = mic; a.sig[1] = ref; a.sig[2] = near;
+    a.ld = ld; a.items = h->d_items; a.nitems = (int64_t)h->lists.items.size();
+    a.num_cus = h->num_cus; a.cvals = cvals; a.slen = h->d_slen;
+    a.tables = reinterpret_cast<const float*>(h->d_tab);
+    a.sched = h->d_sched; a.sched_len = h->sched_len; a.nsig = nsig;
+    a.feats = h->d_feats; a.Tmax = Tmax;
+    return a;
+}
+static SynthArgs synth_args(const aec_handle* h, const float* mic, int64_t ld, int64_t Tmax, const float* cvals,
+                            float* out, int64_t ld_out) {
+    SynthArgs y{};
+    y.mic = mic; y.ld = ld; y.items = h->d_sitems; y.nitems = (int64_t)h->lists.sitems.size(); y.num_cus = h->num_cus;
+    y.cvals = cvals;
+    y.tables = reinterpret_cast<const float*>(h->d_tab);
+    y.bintab = h->d_bintab; y.est = h->d_est; y.Tmax = Tmax;
+    y.out = out; y.ld_out = ld_out;
+    return y;
 }
 
 // Every call that reads or writes the handle's workspace: ordered after the
@@ -626,47 +473,30 @@ static aec_status process_impl(aec_handle* h, uint64_t token, const float* mic, 
     if (B == 0) return AEC_OK;
     if (!mic || !ref) return fail(h, AEC_ERR_INVALID_ARG, "null mic / ref");
     if (loss && !near) return fail(h, AEC_ERR_INVALID_ARG, "loss requires near");
-    const int nsig_in = near ? 3 : 2;
+    const int nsig = near ? 3 : 2;
     int64_t nmax = 0;
-    for (int b = 0; b < B; ++b) {
-        const int64_t n = lengths3[3 * b];
-        for (int s = 0; s < nsig_in; ++s) {
-            const int64_t ns = lengths3[3 * b + s];
-            if (ns < 1 || ns > ld) return fail(h, AEC_ERR_INVALID_ARG, "length out of [1, ld]");
-            if (ns > INT32_MAX - 4096) return fail(h, AEC_ERR_UNSUPPORTED, "stream longer than 2^31 - 4096 samples");
-            // Little_net.forward combines the three signals frame by frame
-            // (ERB.py:287-290, 318-323): the reference raises on a frame-count mismatch
-            if (ns / 256 != n / 256)
-                return fail(h, AEC_ERR_INVALID_ARG, "ref / near frame count differs from mic's (N//256 + 1)");
-        }
-        if (aec_out_len(n) > ld_out) return fail(h, AEC_ERR_INVALID_ARG, "ld_out too small");
-        nmax = n > nmax ? n : nmax;
-    }
+    const Check lc = check_lengths3(lengths3, B, nsig, ld, ld_out, &nmax);
+    if (lc.status != AEC_OK) return fail(h, lc.status, lc.why);
     if (!out && aec_out_len(nmax) > 0) return fail(h, AEC_ERR_INVALID_ARG, "null out");
     const int64_t Tmax = aec_num_frames(nmax);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     AEC_ON_DEVICE(h);
-    const bool nlms_batch = h->cfg.nlms_taps > 0 && !(B <= h->small_b && h->nlms_mode == 0);
-    if (nlms_batch && nlms_smem_bytes(h->sched_len, h->cfg.nlms_taps) > 160 * 1024)   // before any launch
+    // which kernels run (aec_host.h); AEC_GRU_NS is a mode knob read per call
+    const Plan p = plan_call({h->cfg.nlms_taps, B, h->small_b, h->nlms_mode, h->small_pipe, h->fused, h->gru_mode,
+                              h->num_cus, AEC_MODE_KNOB("AEC_GRU_NS", 0), token != 0});
+    if (p.nlms_batch && nlms_smem_bytes(h->sched_len, h->cfg.nlms_taps) > 160 * 1024)   // before any launch
         return fail(h, AEC_ERR_UNSUPPORTED, "erb schedule too long for the NLMS kernel's LDS budget");
-    const int nsig = near ? 3 : 2;
     // aec_process_prepared: the look-ahead pass named by `token` (aec_prepare_siglens), checked
-    // before anything is launched; the pending ones queued before it are dropped (their slots stay
-    // fenced by their done / freed events)
+    // before anything is launched and consumed once nothing before the first launch can fail any
+    // more, so a call that fails with nothing launched leaves it pending (include/aec_hip.h)
+    int pre_k = -1;
     aec_handle::PreSlot* ps = nullptr;
     if (token) {
-        int k = 0;
-        while (k < h->pre_count && h->pre[(h->pre_head + k) & 1].token != token) ++k;
-        if (k == h->pre_count) return fail(h, AEC_ERR_INVALID_ARG, "look-ahead token not pending");
-        aec_handle::PreSlot& c = h->pre[(h->pre_head + k) & 1];
-        if (!(c.sig[0] == mic && c.sig[1] == ref && c.sig[2] == near && c.ld == ld && c.nsig == nsig &&
-              c.l3.size() == (size_t)B * 3 &&
-              std::memcmp(c.l3.data(), lengths3, (size_t)B * 3 * sizeof(int64_t)) == 0))
+        pre_k = h->ring.find(token);
+        if (pre_k < 0) return fail(h, AEC_ERR_INVALID_ARG, "look-ahead token not pending");
+        if (!h->ring.matches(pre_k, mic, ref, near, ld, nsig, lengths3, B))
             return fail(h, AEC_ERR_INVALID_ARG, "look-ahead prepared for other signals / ld / B / lengths");
-        ps = &c;
-        h->pre_head = (h->pre_head + k + 1) & 1;
-        h->pre_count -= k + 1;
-        c.token = 0;
+        ps = &h->pre[h->ring.slot(pre_k)];
     }
     // a consumer of an earlier pipelined launch gave up waiting for its producer: that call's
     // output is invalid; reported once, here
@@ -682,32 +512,13 @@ static aec_status process_impl(aec_handle* h, uint64_t token, const float* mic, 
     CallGuard cg{h, st};
     s = ensure_ws(h, B, Tmax);
     if (s != AEC_OK) return s;
-    s = prepare_lists(h, lengths3, B, nsig_in, st);
+    s = prepare_lists(h, lengths3, B, nsig, st);
     if (s != AEC_OK) return s;
-    // the consumed slot is free again once this call's kernels have read its cvals (every exit)
-    struct PreRelease {
-        aec_handle::PreSlot* ps;
-        hipStream_t st;
-        ~PreRelease() {
-            if (ps && hipEventRecord(ps->freed, st) == hipSuccess) ps->freed_rec = true;
-        }
-    } pre_rel{ps, st};
     const float* cvals = ps ? ps->cvals : h->d_cvals;
-    // the pipelined split path: one GRU + synthesis launch of 2 B blocks (producers first) runs the
-    // recursion and mic_erb too; it needs one block per CU for each and the one tap count it is
-    // built for, and runs the GRU one stream per block (the AEC_GRU_NS rule for small batches)
-    const bool pipe = h->small_pipe && h->cfg.nlms_taps == kPipeTaps && B <= h->small_b && h->nlms_mode == 0 &&
-                      h->fused && h->gru_mode == 0 && 2 * (int64_t)B <= (int64_t)h->num_cus &&
-                      AEC_MODE_KNOB("AEC_GRU_NS", 0) != 2;
-    if (pipe) {
+    if (p.pipe) {
         if (B > h->progress_cap) {
-            if (h->have_last) HIP_TRY(h, hipEventSynchronize(h->ev_last));
-            if (h->d_progress) HIP_TRY(h, hipFree(h->d_progress));
-            h->d_progress = nullptr;
-            h->progress_cap = 0;
-            HIP_TRY(h, hipMalloc(&h->d_progress, (size_t)B * sizeof(unsigned long long)));
-            HIP_TRY(h, hipMemset(h->d_progress, 0, (size_t)B * sizeof(unsigned long long)));
-            h->progress_cap = B;
+            s = grow_after_last(h, h->d_progress, h->progress_cap, B, (size_t)B * sizeof(unsigned long long), true);
+            if (s != AEC_OK) return s;
         }
         if (!h->h_pipe_err) {
             HIP_TRY(h, hipHostMalloc(reinterpret_cast<void**>(&h->h_pipe_err), sizeof(int), hipHostMallocMapped));
@@ -717,50 +528,30 @@ static aec_status process_impl(aec_handle* h, uint64_t token, const float* mic, 
     }
     if (ps) HIP_TRY(h, hipStreamWaitEvent(st, ps->done, 0));
     mark(h, st);
-    // the NLMS split path's K2 takes the normaliser scalars straight from the moment partials (the
-    // same expression as norm_finalize_kernel): one launch fewer on the latency-bound small batches
-    const bool split = h->cfg.nlms_taps > 0 && B <= h->small_b && h->nlms_mode == 0;
-    // the bypass path (no NLMS) with up to half the CUs of streams: GRU + synthesis fused (one stream
-    // per block) over K2's mic rows instead of gru_kernel + synthesis_kernel re-deriving the mic
-    // spectrum (the same values, tested bit-exact)
-    const bool bypass_fused = h->cfg.nlms_taps == 0 && h->fused && h->gru_mode == 0 &&
-                              2 * (int64_t)B <= (int64_t)h->num_cus;
-    const bool fold_norm = (split || bypass_fused) && !ps;
     if (!ps) {
         HIP_TRY(h, launch_moments(mic, ref, near, ld, h->d_slen, h->d_mom, 0, B, nsig, st));
-        if (!fold_norm) HIP_TRY(h, launch_norm_finalize(h->d_mom, h->d_slen, h->d_cvals, 0, B, nsig, st));
+        if (!p.fold_norm) HIP_TRY(h, launch_norm_finalize(h->d_mom, h->d_slen, h->d_cvals, 0, B, nsig, st));
     }
-    if (split || bypass_fused) {
-        // packed mic / ref rows of K2
+    const bool rows = p.split || p.bypass_fused;      // K2 also writes its packed mic / ref rows
+    if (rows) {
         const size_t need = (size_t)B * Tmax * 512 + (size_t)B * 256;      // + one dummy row per stream
         if (need > h->rows_cap) {
-            if (h->have_last) HIP_TRY(h, hipEventSynchronize(h->ev_last));
-            if (h->d_rows) HIP_TRY(h, hipFree(h->d_rows));
-            h->d_rows = nullptr;
-            h->rows_cap = 0;
-            HIP_TRY(h, hipMalloc(&h->d_rows, need * sizeof(float2)));
-            h->rows_cap = need;
+            s = grow_after_last(h, h->d_rows, h->rows_cap, need, need * sizeof(float2));
+            if (s != AEC_OK) return s;
         }
     }
-    if (split) {
-        // few streams: transforms frame-parallel (K2 + rows), recursion per stream, mic_erb frame-parallel
-        AnalysisArgs a{};
-        a.sig[0] = mic; a.sig[1] = ref; a.sig[2] = near;
-        a.ld = ld; a.items = h->d_items; a.nitems = h->nitems;
-        a.num_cus = h->num_cus; a.cvals = fold_norm ? nullptr : cvals; a.mom = h->d_mom; a.slen = h->d_slen;
-        a.tables = reinterpret_cast<const float*>(h->d_tab);
-        a.sched = h->d_sched; a.sched_len = h->sched_len; a.nsig = nsig;
-        a.feats = h->d_feats; a.Tmax = Tmax; a.rows = h->d_rows;
-        mark(h, st);
-        HIP_TRY(h, launch_analysis(a, st));
-        if (!pipe) {
-            HIP_TRY(h, launch_nlms_recursion(h->d_rows, h->d_spec, h->d_len, Tmax, h->cfg.nlms_taps, h->cfg.nlms_mu,
-                                             h->cfg.nlms_beta, h->cfg.nlms_delta, 0, B,
-                                             h->d_rows + (size_t)B * Tmax * 512, st));
-            HIP_TRY(h, launch_mic_erb(h->d_spec, h->d_feats, h->d_len, Tmax, h->d_sched, h->sched_len, h->d_items,
-                                      h->nitems, st));
+    // the last return with nothing launched is behind: the look-ahead is consumed, and the pending
+    // passes queued before it are dropped (their slots stay fenced by their done / freed events)
+    if (ps) h->ring.consume(pre_k);
+    // the consumed slot is free again once this call's kernels have read its cvals (every exit from here)
+    struct PreRelease {
+        aec_handle::PreSlot* ps;
+        hipStream_t st;
+        ~PreRelease() {
+            if (ps && hipEventRecord(ps->freed, st) == hipSuccess) ps->freed_rec = true;
         }
-    } else if (h->cfg.nlms_taps > 0) {
+    } pre_rel{ps, st};
+    if (p.nlms_batch) {
         NlmsArgs a{};
         a.sig[0] = mic; a.sig[1] = ref; a.sig[2] = near;
         a.ld = ld; a.lens = h->d_len; a.slen = h->d_slen; a.b0 = 0; a.cvals = cvals;
@@ -774,16 +565,20 @@ static aec_status process_impl(aec_handle* h, uint64_t token, const float* mic, 
         mark(h, st);
         HIP_TRY(h, launch_nlms_analysis(a, B, st));
     } else {
-        AnalysisArgs a{};
-        a.sig[0] = mic; a.sig[1] = ref; a.sig[2] = near;
-        a.ld = ld; a.items = h->d_items; a.nitems = h->nitems;
-        a.num_cus = h->num_cus; a.cvals = fold_norm ? nullptr : cvals; a.mom = h->d_mom; a.slen = h->d_slen;
-        a.tables = reinterpret_cast<const float*>(h->d_tab);
-        a.sched = h->d_sched; a.sched_len = h->sched_len; a.nsig = nsig;
-        a.feats = h->d_feats; a.Tmax = Tmax;
-        if (bypass_fused) a.rows = h->d_rows;
+        // K2, frame-parallel; with fold_norm it takes the normaliser scalars straight from the moment
+        // partials (norm_finalize_kernel's expression)
+        AnalysisArgs a = analysis_args(h, mic, ref, near, ld, nsig, Tmax, p.fold_norm ? nullptr : cvals);
+        a.mom = h->d_mom;
+        if (rows) a.rows = h->d_rows;
         mark(h, st);
         HIP_TRY(h, launch_analysis(a, st));
+        if (p.split && !p.pipe) {      // few streams: recursion per stream, then mic_erb frame-parallel
+            HIP_TRY(h, launch_nlms_recursion(h->d_rows, h->d_spec, h->d_len, Tmax, h->cfg.nlms_taps, h->cfg.nlms_mu,
+                                             h->cfg.nlms_beta, h->cfg.nlms_delta, 0, B,
+                                             h->d_rows + (size_t)B * Tmax * 512, st));
+            HIP_TRY(h, launch_mic_erb(h->d_spec, h->d_feats, h->d_len, Tmax, h->d_sched, h->sched_len, h->d_items,
+                                      a.nitems, st));
+        }
     }
     mark(h, st);
 
@@ -795,16 +590,11 @@ static aec_status process_impl(aec_handle* h, uint64_t token, const float* mic, 
     g.mode = h->gru_mode;
     g.b0 = 0;
 
-    SynthArgs y{};
-    y.mic = mic; y.ld = ld; y.items = h->d_sitems; y.nitems = h->nsitems; y.num_cus = h->num_cus;
-    y.cvals = cvals;
-    y.tables = reinterpret_cast<const float*>(h->d_tab);
-    y.bintab = h->d_bintab; y.est = h->d_est; y.Tmax = Tmax;
-    y.out = out; y.ld_out = ld_out;
-    y.spec = h->cfg.nlms_taps > 0 ? h->d_spec : (bypass_fused ? h->d_rows : nullptr);
-    y.spec_stride = bypass_fused ? 512 : 256;
+    SynthArgs y = synth_args(h, mic, ld, Tmax, cvals, out, ld_out);
+    y.spec = h->cfg.nlms_taps > 0 ? h->d_spec : (p.bypass_fused ? h->d_rows : nullptr);
+    y.spec_stride = p.bypass_fused ? 512 : 256;
     y.fmode = h->fused_mode;
-    if (pipe) {
+    if (p.pipe) {
         PipeArgs q{};
         q.rows = h->d_rows; q.spec = h->d_spec; q.feats = h->d_feats;
         q.sched = h->d_sched; q.sched_len = h->sched_len;
@@ -823,7 +613,7 @@ static aec_status process_impl(aec_handle* h, uint64_t token, const float* mic, 
         mark(h, st);
     } else if (y.spec && h->fused && h->gru_mode == 0) {
         // one kernel: the synthesis runs two chunks behind the recurrence
-        HIP_TRY(h, launch_gru_synth(g, y, B, st));
+        HIP_TRY(h, launch_gru_synth(g, y, B, p.gru_one, st));
         mark(h, st);
         mark(h, st);
     } else {
@@ -842,21 +632,13 @@ aec_status aec_prepare_siglens(aec_handle* h, const float* mic, const float* ref
     if (!h) return AEC_ERR_INVALID_ARG;
     if (token) *token = 0;
     if (B <= 0 || !lengths3 || !mic || !ref) return fail(h, AEC_ERR_INVALID_ARG, "bad batch / lengths / signals");
-    if (h->pre_count >= 2) return fail(h, AEC_ERR_INVALID_ARG, "two look-ahead batches already pending");
+    if (h->ring.full()) return fail(h, AEC_ERR_INVALID_ARG, "two look-ahead batches already pending");
     const int nsig = near ? 3 : 2;
-    for (int b = 0; b < B; ++b) {
-        const int64_t n = lengths3[3 * b];
-        for (int sg = 0; sg < nsig; ++sg) {
-            const int64_t ns = lengths3[3 * b + sg];
-            if (ns < 1 || ns > ld) return fail(h, AEC_ERR_INVALID_ARG, "length out of [1, ld]");
-            if (ns > INT32_MAX - 4096) return fail(h, AEC_ERR_UNSUPPORTED, "stream longer than 2^31 - 4096 samples");
-            if (ns / 256 != n / 256)
-                return fail(h, AEC_ERR_INVALID_ARG, "ref / near frame count differs from mic's (N//256 + 1)");
-        }
-    }
+    const Check lc = check_lengths3(lengths3, B, nsig, ld);
+    if (lc.status != AEC_OK) return fail(h, lc.status, lc.why);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     AEC_ON_DEVICE(h);
-    aec_handle::PreSlot& ps = h->pre[(h->pre_head + h->pre_count) & 1];
+    aec_handle::PreSlot& ps = h->pre[h->ring.slot(h->ring.count)];      // the slot push() records below
     if (ps.used) HIP_TRY(h, hipEventSynchronize(ps.done));      // its staging copy has been read
     if (B > ps.cap) {
         if (ps.freed_rec) HIP_TRY(h, hipEventSynchronize(ps.freed));
@@ -875,23 +657,14 @@ aec_status aec_prepare_siglens(aec_handle* h, const float* mic, const float* ref
     // the call that consumed this slot last has read its cvals; a dropped pass into it has finished
     if (ps.freed_rec) HIP_TRY(h, hipStreamWaitEvent(st, ps.freed, 0));
     if (ps.used) HIP_TRY(h, hipStreamWaitEvent(st, ps.done, 0));
-    for (int b = 0; b < B; ++b) {   // prepare_lists' per-signal lengths
-        for (int sg = 0; sg < 3; ++sg)
-            ps.host[4 * b + sg] = (int32_t)(sg < nsig ? lengths3[3 * b + sg] : lengths3[3 * b]);
-        ps.host[4 * b + 3] = 0;
-    }
+    fill_slen(ps.host, lengths3, B, nsig);
     HIP_TRY(h, hipMemcpyAsync(ps.slen, ps.host, (size_t)B * 4 * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIP_TRY(h, launch_moments(mic, ref, near, ld, ps.slen, ps.mom, 0, B, nsig, st));
     HIP_TRY(h, launch_norm_finalize(ps.mom, ps.slen, ps.cvals, 0, B, nsig, st));
     HIP_TRY(h, hipEventRecord(ps.done, st));
     ps.used = true;
-    ps.sig[0] = mic; ps.sig[1] = ref; ps.sig[2] = near;
-    ps.ld = ld;
-    ps.nsig = nsig;
-    ps.l3.assign(lengths3, lengths3 + (size_t)B * 3);
-    ps.token = h->next_token++;
-    if (token) *token = ps.token;
-    ++h->pre_count;
+    const uint64_t tk = h->ring.push(mic, ref, near, ld, nsig, lengths3, B);
+    if (token) *token = tk;
     return AEC_OK;
 }
 
@@ -961,29 +734,8 @@ aec_status aec_erb_tables_check(const float* erb, const float* mags, const float
     if (!erb || !mags || !est || !bands || !gains) return AEC_ERR_INVALID_ARG;
     const ErbTables t = build_erb_tables(erb);
     if (!t.ok) return AEC_ERR_UNSUPPORTED;
-    const int L = t.sched_len;
-    float part[48];
-    for (int l = 0; l < 16; ++l) {
-        float a[3] = {0.f, 0.f, 0.f};
-        for (int e = 0; e < L; ++e) {
-            const float* en = &t.sched[((size_t)e * 16 + l) * 4];
-            int k;
-            std::memcpy(&k, en, 4);
-            for (int s = 0; s < 3; ++s) a[s] = std::fma(en[1 + s], mags[k], a[s]);
-        }
-        for (int s = 0; s < 3; ++s) part[3 * l + s] = a[s];
-    }
-    int comb[64];
-    std::memcpy(comb, &t.sched[(size_t)L * 16 * 4], sizeof(comb));
-    for (int j = 0; j < 32; ++j) bands[j] = part[comb[2 * j]] + (comb[2 * j + 1] >= 0 ? part[comb[2 * j + 1]] : 0.f);
-    for (int k = 0; k < 257; ++k) {
-        const float* e = &t.bintab[k * 4];
-        int ja, jb;
-        std::memcpy(&ja, &e[0], 4);
-        std::memcpy(&jb, &e[2], 4);
-        gains[k] = e[1] * est[ja] + e[3] * est[jb];
-    }
-    if (sched_len) *sched_len = L;
+    erb_tables_apply(t, mags, est, bands, gains);
+    if (sched_len) *sched_len = t.sched_len;
     if (conflicts) *conflicts = t.conflicts;
     return AEC_OK;
 }
@@ -1092,13 +844,7 @@ aec_status aec_train_forward(aec_handle* h, const float* mic, const float* ref, 
     const int64_t Tmax = T;
     HIP_TRY(h, launch_moments(mic, ref, near, ld, h->d_slen, h->d_mom, 0, B, 3, st));
     HIP_TRY(h, launch_norm_global(h->d_mom, B, n, h->d_cvals, st));
-    AnalysisArgs a{};
-    a.sig[0] = mic; a.sig[1] = ref; a.sig[2] = near;
-    a.ld = ld; a.items = h->d_items; a.nitems = h->item_off[B];
-    a.num_cus = h->num_cus; a.cvals = h->d_cvals; a.slen = h->d_slen;
-    a.tables = reinterpret_cast<const float*>(h->d_tab);
-    a.sched = h->d_sched; a.sched_len = h->sched_len; a.nsig = 3;
-    a.feats = h->d_feats; a.Tmax = Tmax;
+    const AnalysisArgs a = analysis_args(h, mic, ref, near, ld, 3, Tmax, h->d_cvals);
     HIP_TRY(h, launch_analysis(a, st));
     GruArgs g{};
     g.feats = h->d_feats; g.Tmax = Tmax; g.lens = h->d_len; g.w = h->d_w;
@@ -1108,12 +854,7 @@ aec_status aec_train_forward(aec_handle* h, const float* mic, const float* ref, 
     g.b0 = 0;
     HIP_TRY(h, launch_gru(g, B, st));
     if (out) {
-        SynthArgs y{};
-        y.mic = mic; y.ld = ld; y.items = h->d_sitems; y.nitems = h->sitem_off[B]; y.num_cus = h->num_cus;
-        y.cvals = h->d_cvals;
-        y.tables = reinterpret_cast<const float*>(h->d_tab);
-        y.bintab = h->d_bintab; y.est = h->d_est; y.Tmax = Tmax;
-        y.out = out; y.ld_out = ld_out;
+        const SynthArgs y = synth_args(h, mic, ld, Tmax, h->d_cvals, out, ld_out);
         HIP_TRY(h, launch_synthesis(y, st));
     }
     HIP_TRY(h, launch_loss_sum(h->d_tloss, B, loss, st));
@@ -1161,14 +902,17 @@ aec_status aec_train_backward(aec_handle* h, const float* grad_loss, float* grad
     return cg.end();
 }
 
+static bool adam_in_range(float lr, float beta1, float beta2, float eps, float weight_decay) {   // NaN: out
+    return lr >= 0.f && beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f && weight_decay >= 0.f;
+}
+
 aec_status aec_adam_step(aec_handle* h, float* params, const float* grad, float* exp_avg, float* exp_avg_sq,
                          size_t n, int64_t step, float lr, float beta1, float beta2, float eps, float weight_decay,
                          void* stream) {
     if (!h) return AEC_ERR_INVALID_ARG;
     if (!params || !grad || !exp_avg || !exp_avg_sq) return fail(h, AEC_ERR_INVALID_ARG, "null buffer");
     if (step < 1) return fail(h, AEC_ERR_INVALID_ARG, "step counts from 1");
-    if (!(lr >= 0.f) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps >= 0.f) ||
-        !(weight_decay >= 0.f))
+    if (!adam_in_range(lr, beta1, beta2, eps, weight_decay))
         return fail(h, AEC_ERR_INVALID_ARG, "Adam hyper-parameters out of range");
     AEC_ON_DEVICE(h);
     // torch/optim/adam.py computes the bias corrections in double on the host
@@ -1185,8 +929,7 @@ aec_status aec_adam_step_multi(aec_handle* h, float* const* params, const float*
     if (!h) return AEC_ERR_INVALID_ARG;
     if (count < 0 || (count > 0 && (!params || !grads || !exp_avg || !exp_avg_sq || !sizes || !steps)))
         return fail(h, AEC_ERR_INVALID_ARG, "null tensor list");
-    if (!(lr >= 0.f) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps >= 0.f) ||
-        !(weight_decay >= 0.f))
+    if (!adam_in_range(lr, beta1, beta2, eps, weight_decay))
         return fail(h, AEC_ERR_INVALID_ARG, "Adam hyper-parameters out of range");
     AEC_ON_DEVICE(h);
     for (int32_t c0 = 0; c0 < count; c0 += kAdamMax) {

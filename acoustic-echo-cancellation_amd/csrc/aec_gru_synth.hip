@@ -748,14 +748,12 @@ static unsigned long long wmap_ns1(int wm) {
 // C2 step 1.3 % faster).  So NS = 1 while the batch fills at most half the CUs (the
 // latency-bound calls: batch 1 0.454 -> 0.364 ms, 64 streams 0.588 -> 0.479 ms,
 // profiles/r06h_b1.log), NS = 2 above.  AEC_GRU_NS = 1 / 2 forces one (a mode knob, read per
-// launch; the two are bit-identical in the waveform and est_erb, the loss is summed in another
-// order, <= 1e-6 relative).
-hipError_t launch_gru_synth(const GruArgs& g, const SynthArgs& y, int B, hipStream_t st) {
+// call; the two are bit-identical in the waveform and est_erb, the loss is summed in another
+// order, <= 1e-6 relative).  The caller decides (`one`: plan_call, aec_host.h).
+hipError_t launch_gru_synth(const GruArgs& g, const SynthArgs& y, int B, bool one, hipStream_t st) {
     if (B <= 0) return hipSuccess;
     // NS = 2 writes the waveform with 16-B stores (overlap-add on the recurrence waves)
     const bool al16 = y.ld_out % 4 == 0 && (reinterpret_cast<uintptr_t>(y.out) & 15) == 0;
-    const int force = AEC_MODE_KNOB("AEC_GRU_NS", 0);
-    const bool one = force == 1 || (force != 2 && 2 * (int64_t)B <= (int64_t)std::max(y.num_cus, 2));
     const int ns = one || (AEC_OLA_REC && !al16) ? 1 : 2;
     SynthArgs ya = y;
     ya.wmap = 0;

@@ -1,0 +1,395 @@
+// aec_host.h — the C ABI's host-side call planning: ERB tables, length checks,
+// work lists, path selection and the look-ahead ring.  Plain C++17 with no HIP
+// in it, so a host compiler builds it alone and tests/host/aec_host_check.cpp
+// runs it under the CPU sanitizers; aec_api.hip does the launches.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <functional>
+#include <vector>
+
+#include "../../include/aec_hip.h"
+
+namespace aec {
+
+constexpr int kFPB = 16;            // frames per analysis / synthesis block (16 groups x 16 lanes)
+constexpr int kHopsOut = kFPB - 1;  // output hops per synthesis block
+constexpr int kPipeTaps = 4;        // the one tap count the small-batch pipeline is instantiated for
+
+inline int64_t num_frames(int64_t n) { return n / 256 + 1; }
+inline int64_t out_len(int64_t n) { return 256 * (n / 256); }
+
+// ---------------------------------------------------------------------------
+// ERB tables: balanced forward schedule + transpose table
+// ---------------------------------------------------------------------------
+// ERB matrix views.  The reference multiplies the dense [257,32] float32
+// matrix (ERB.py:282-284 forward, :306-307 transpose); only its non-zeros
+// (483 for erb_conf) matter, and every bin lies in at most 2 bands.
+//
+// Forward (bins -> bands), analysis kernel: a per-lane schedule for the 16
+// lanes of a frame group.  Bands wider than `split` bins are cut into two
+// pieces; the pieces are packed (first-fit decreasing, <= 3 pieces per lane)
+// so every lane runs the same L entries.  Entry = float4(bin as int bits,
+// w0, w1, w2): exactly one of w0..w2 is the matrix value (the piece's slot
+// in that lane), the others are 0, so the lane does 3 FMAs and no selects.
+// comb[j] = (slot index of piece 0, slot index of piece 1 or -1), slot index
+// = 3*lane + slot.  Blob = float4[L][16] followed by int2[32].
+//
+// Transpose (bands -> bins), synthesis kernel: float4[257] =
+// (band_a as int bits, w_a, band_b as int bits, w_b); w_b = 0 when the bin is
+// in one band, both 0 when in none (DC / Nyquist).
+struct ErbTables {
+    int sched_len = 0;
+    int conflicts = 0;           // (step, lane) entries that could not get a distinct residue
+    std::vector<float> sched;    // 16 * 4 * L floats + 64 ints (as floats)
+    std::vector<float> bintab;   // 257 * 4
+    bool ok = false;
+    const char* why = "";
+};
+
+inline ErbTables build_erb_tables(const float* erb /* [257][32] */) {
+    const int NB = 32, NF = 257, LANES = 16, SLOTS = 3;
+    ErbTables t;
+    std::vector<std::vector<int>> bins(NB);
+    int maxw = 0, nnz = 0;
+    for (int j = 0; j < NB; ++j) {
+        for (int k = 0; k < NF; ++k)
+            if (erb[k * NB + j] != 0.f) bins[j].push_back(k);
+        maxw = std::max(maxw, (int)bins[j].size());
+        nnz += (int)bins[j].size();
+    }
+    // transpose table: <= 2 bands per bin
+    t.bintab.assign(NF * 4, 0.f);
+    for (int k = 0; k < NF; ++k) {
+        int cnt = 0;
+        for (int j = 0; j < NB; ++j) {
+            const float v = erb[k * NB + j];
+            if (v == 0.f) continue;
+            if (cnt == 2) { t.why = "a bin lies in more than 2 bands"; return t; }
+            int ib = j;
+            std::memcpy(&t.bintab[k * 4 + 2 * cnt], &ib, 4);
+            t.bintab[k * 4 + 2 * cnt + 1] = v;
+            ++cnt;
+        }
+        if (cnt == 1) { int ib; std::memcpy(&ib, &t.bintab[k * 4], 4); std::memcpy(&t.bintab[k * 4 + 2], &ib, 4); }
+    }
+    // forward schedule: split bands wider than `split` in two, pack pieces
+    struct Piece { int band, first, count; };
+    for (int split = std::max(26, (maxw + 1) / 2); split <= NF; split += 2) {
+        std::vector<Piece> pieces;
+        for (int j = 0; j < NB; ++j) {
+            const int w = (int)bins[j].size();
+            if (w == 0) continue;
+            if (w > split) {
+                pieces.push_back({j, 0, (w + 1) / 2});
+                pieces.push_back({j, (w + 1) / 2, w - (w + 1) / 2});
+            } else {
+                pieces.push_back({j, 0, w});
+            }
+        }
+        std::stable_sort(pieces.begin(), pieces.end(), [](const Piece& a, const Piece& b) { return a.count > b.count; });
+        std::vector<std::vector<int>> lane(LANES);
+        std::vector<int> load(LANES, 0);
+        bool fits = true;
+        for (int p = 0; p < (int)pieces.size() && fits; ++p) {
+            int best = -1;
+            for (int l = 0; l < LANES; ++l)
+                if ((int)lane[l].size() < SLOTS && (best < 0 || load[l] < load[best])) best = l;
+            if (best < 0) fits = false;
+            else { lane[best].push_back(p); load[best] += pieces[p].count; }
+        }
+        if (!fits) continue;
+        int L = 0;
+        for (int l = 0; l < LANES; ++l) L = std::max(L, load[l]);
+        L = (L + 3) & ~3;
+        if (L > 48) { t.why = "ERB schedule longer than 48 entries per lane"; return t; }
+        t.sched_len = L;
+        t.sched.assign((size_t)L * LANES * 4 + 64, 0.f);
+        std::vector<int> comb(2 * NB, -1);
+        // Order every lane's entries so that at each step the 16 lanes read
+        // bins with distinct residues mod 16: with the per-frame XOR swizzle the
+        // 32 lanes of a ds_read_b32 then hit 32 distinct banks.  One bipartite
+        // matching (lanes x residues, Kuhn) per step; lanes with no slack left
+        // must take a real entry, the others may take a zero-weight padding
+        // entry on a free residue (bin = residue).
+        struct Item { int k, s; float w; };
+        std::vector<std::vector<Item>> items(LANES);
+        for (int l = 0; l < LANES; ++l)
+            for (int s = 0; s < (int)lane[l].size(); ++s) {
+                const Piece& pc = pieces[lane[l][s]];
+                for (int i = 0; i < pc.count; ++i) {
+                    const int k = bins[pc.band][pc.first + i];
+                    items[l].push_back({k, s, erb[k * NB + pc.band]});
+                }
+                const int slot = 3 * l + s;
+                if (comb[2 * pc.band] < 0) comb[2 * pc.band] = slot;
+                else comb[2 * pc.band + 1] = slot;
+            }
+        t.conflicts = 0;
+        for (int e = 0; e < L; ++e) {
+            const int left = L - e;
+            std::vector<int> owner(16, -1), match(LANES, -1);
+            std::vector<int> order(LANES);
+            for (int l = 0; l < LANES; ++l) order[l] = l;
+            std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
+                return left - (int)items[a].size() < left - (int)items[b].size(); });
+            std::function<bool(int, std::vector<char>&)> aug = [&](int l, std::vector<char>& seen) -> bool {
+                for (const Item& it : items[l]) {
+                    const int r = it.k & 15;
+                    if (seen[r]) continue;
+                    seen[r] = 1;
+                    if (owner[r] < 0 || aug(owner[r], seen)) { owner[r] = l; match[l] = r; return true; }
+                }
+                return false;
+            };
+            for (int l : order) {
+                if (items[l].empty()) continue;
+                std::vector<char> seen(16, 0);
+                aug(l, seen);
+            }
+            for (int l = 0; l < LANES; ++l) {
+                float* en = &t.sched[((size_t)e * LANES + l) * 4];
+                if (match[l] >= 0) {
+                    for (size_t i = 0; i < items[l].size(); ++i)
+                        if ((items[l][i].k & 15) == match[l]) {
+                            const Item it = items[l][i];
+                            std::memcpy(&en[0], &it.k, 4);
+                            en[1 + it.s] = it.w;
+                            items[l].erase(items[l].begin() + i);
+                            break;
+                        }
+                } else if ((int)items[l].size() >= left) {       // no slack: take one anyway
+                    const Item it = items[l].front();
+                    std::memcpy(&en[0], &it.k, 4);
+                    en[1 + it.s] = it.w;
+                    items[l].erase(items[l].begin());
+                    ++t.conflicts;
+                } else {                                          // zero-weight padding on a free residue
+                    int r = 0;
+                    while (owner[r] >= 0) ++r;
+                    owner[r] = l;
+                    std::memcpy(&en[0], &r, 4);
+                }
+            }
+        }
+        // bands with no non-zeros read a zero slot: point both at a lane with < 3 pieces, else -1 pair
+        for (int j = 0; j < NB; ++j) {
+            if (comb[2 * j] < 0) {
+                int z = -1;
+                for (int l = 0; l < LANES && z < 0; ++l)
+                    if ((int)lane[l].size() < SLOTS) z = 3 * l + (int)lane[l].size();
+                if (z < 0) { t.why = "no zero slot for an empty band"; return t; }
+                comb[2 * j] = z;
+            }
+        }
+        std::memcpy(&t.sched[(size_t)L * LANES * 4], comb.data(), 64 * 4);
+        t.ok = true;
+        return t;
+    }
+    t.why = "could not balance the ERB schedule";
+    return t;
+}
+
+// The tables evaluated as the kernels evaluate them (aec_erb_tables_check):
+// bands[32] = mags[257] through the schedule, gains[257] = est[32] through the
+// transpose table.
+inline void erb_tables_apply(const ErbTables& t, const float* mags, const float* est, float* bands, float* gains) {
+    const int L = t.sched_len;
+    float part[48];
+    for (int l = 0; l < 16; ++l) {
+        float a[3] = {0.f, 0.f, 0.f};
+        for (int e = 0; e < L; ++e) {
+            const float* en = &t.sched[((size_t)e * 16 + l) * 4];
+            int k;
+            std::memcpy(&k, en, 4);
+            for (int s = 0; s < 3; ++s) a[s] = std::fma(en[1 + s], mags[k], a[s]);
+        }
+        for (int s = 0; s < 3; ++s) part[3 * l + s] = a[s];
+    }
+    int comb[64];
+    std::memcpy(comb, &t.sched[(size_t)L * 16 * 4], sizeof(comb));
+    for (int j = 0; j < 32; ++j) bands[j] = part[comb[2 * j]] + (comb[2 * j + 1] >= 0 ? part[comb[2 * j + 1]] : 0.f);
+    for (int k = 0; k < 257; ++k) {
+        const float* e = &t.bintab[k * 4];
+        int ja, jb;
+        std::memcpy(&ja, &e[0], 4);
+        std::memcpy(&jb, &e[2], 4);
+        gains[k] = e[1] * est[ja] + e[3] * est[jb];
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Per-signal lengths [B][3] (mic, ref, near)
+// ---------------------------------------------------------------------------
+struct Check {
+    aec_status status = AEC_OK;
+    const char* why = "";
+};
+
+// The first `nsig` entries of every row, and the row's output length against
+// ld_out (INT64_MAX: no output yet, aec_prepare_siglens).  *nmax (optional)
+// receives the longest mic length.
+inline Check check_lengths3(const int64_t* lengths3, int32_t B, int nsig, int64_t ld, int64_t ld_out = INT64_MAX,
+                            int64_t* nmax = nullptr) {
+    int64_t m = 0;
+    for (int b = 0; b < B; ++b) {
+        const int64_t n = lengths3[3 * b];
+        for (int s = 0; s < nsig; ++s) {
+            const int64_t ns = lengths3[3 * b + s];
+            if (ns < 1 || ns > ld) return {AEC_ERR_INVALID_ARG, "length out of [1, ld]"};
+            if (ns > INT32_MAX - 4096) return {AEC_ERR_UNSUPPORTED, "stream longer than 2^31 - 4096 samples"};
+            // Little_net.forward combines the three signals frame by frame
+            // (ERB.py:287-290, 318-323): the reference raises on a frame-count mismatch
+            if (ns / 256 != n / 256)
+                return {AEC_ERR_INVALID_ARG, "ref / near frame count differs from mic's (N//256 + 1)"};
+        }
+        if (out_len(n) > ld_out) return {AEC_ERR_INVALID_ARG, "ld_out too small"};
+        m = n > m ? n : m;
+    }
+    if (nmax) *nmax = m;
+    return {};
+}
+
+// dst[B][4] = (mic, ref, near, 0) lengths as the kernels read them (normaliser
+// + zero padding); a signal that is not given takes mic's length
+inline void fill_slen(int32_t* dst, const int64_t* lengths3, int32_t B, int nsig) {
+    for (int b = 0; b < B; ++b) {
+        for (int sg = 0; sg < 3; ++sg) dst[4 * b + sg] = (int32_t)lengths3[3 * b + (sg < nsig ? sg : 0)];
+        dst[4 * b + 3] = 0;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Work lists of a batch
+// ---------------------------------------------------------------------------
+// One work item: analysis, 4 consecutive frames [wt, wt+4) of stream b (length
+// n); synthesis, kHopsOut output hops from hop wt.
+struct WorkItem {
+    int32_t b;
+    int32_t wt;
+    int64_t n;
+};
+
+inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+struct WorkLists {
+    std::vector<WorkItem> items, sitems;        // analysis (valid frames only) / synthesis
+    std::vector<int64_t> item_off, sitem_off;   // first item of stream b (B + 1 entries)
+    // the device block [items | sitems | len[B] int64 | slen[B][4] int32], 16-B aligned pieces
+    size_t o_si = 0, o_len = 0, o_slen = 0, bytes = 0;
+};
+
+inline WorkLists build_work_lists(const int64_t* lengths3, int32_t B) {
+    WorkLists w;
+    w.item_off.assign(B + 1, 0);
+    w.sitem_off.assign(B + 1, 0);
+    for (int b = 0; b < B; ++b) {
+        const int64_t n = lengths3[3 * b];
+        w.item_off[b] = (int64_t)w.items.size();
+        for (int64_t wt = 0; wt < num_frames(n); wt += 4) w.items.push_back({b, (int32_t)wt, n});
+        w.sitem_off[b] = (int64_t)w.sitems.size();
+        for (int64_t h0 = 0; h0 < n / 256; h0 += kHopsOut) w.sitems.push_back({b, (int32_t)h0, n});
+    }
+    w.item_off[B] = (int64_t)w.items.size();
+    w.sitem_off[B] = (int64_t)w.sitems.size();
+    w.o_si = align16(w.items.size() * sizeof(WorkItem));
+    w.o_len = w.o_si + align16(w.sitems.size() * sizeof(WorkItem));
+    w.o_slen = w.o_len + align16((size_t)B * sizeof(int64_t));
+    w.bytes = w.o_slen + align16((size_t)B * 4 * sizeof(int32_t));
+    return w;
+}
+
+// ---------------------------------------------------------------------------
+// Path selection of one aec_process* call
+// ---------------------------------------------------------------------------
+struct PlanIn {
+    int nlms_taps;
+    int32_t B;
+    int small_b;        // AEC_SMALLB, resolved (default: half the CUs)
+    int nlms_mode, small_pipe, fused, gru_mode;
+    int num_cus;
+    int gru_ns;         // AEC_GRU_NS as read for this call: 0 by the batch size, 1 / 2 forced
+    bool lookahead;     // the call consumes a look-ahead normaliser pass
+};
+struct Plan {
+    bool nlms_batch;    // K2n: one block per stream runs transforms + recursion
+    bool split;         // few streams: K2 with rows, recursion per stream, mic_erb frame-parallel
+    bool pipe;          // split, with the recursion and mic_erb in producer blocks of the GRU + synthesis
+                        // launch: one block per CU for each, the one tap count it is built for, NS = 1
+    bool bypass_fused;  // no NLMS, up to half the CUs of streams: GRU + synthesis fused over K2's mic rows
+    bool fold_norm;     // K2 takes the normaliser scalars from the moment partials (no norm_finalize launch)
+    bool gru_one;       // the fused GRU + synthesis runs one stream per block (NS = 1), else two
+};
+
+inline Plan plan_call(const PlanIn& in) {
+    const bool small = in.B <= in.small_b && in.nlms_mode == 0;
+    const bool fused = in.fused && in.gru_mode == 0;
+    const bool half = 2 * (int64_t)in.B <= (int64_t)in.num_cus;
+    Plan p;
+    p.nlms_batch = in.nlms_taps > 0 && !small;
+    p.split = in.nlms_taps > 0 && small;
+    p.pipe = in.small_pipe && in.nlms_taps == kPipeTaps && small && fused && half && in.gru_ns != 2;
+    p.bypass_fused = in.nlms_taps == 0 && fused && half;
+    p.fold_norm = (p.split || p.bypass_fused) && !in.lookahead;
+    p.gru_one = in.gru_ns == 1 || (in.gru_ns != 2 && 2 * (int64_t)in.B <= (int64_t)std::max(in.num_cus, 2));
+    return p;
+}
+
+// ---------------------------------------------------------------------------
+// Look-ahead ring: the host record of the (at most two) pending
+// aec_prepare_siglens passes, oldest first.  Entry k (0 = oldest) lives in
+// slot(k), which also indexes the handle's device resources of that pass.
+// ---------------------------------------------------------------------------
+struct PreRing {
+    struct Entry {
+        uint64_t token = 0;
+        const float* sig[3] = {nullptr, nullptr, nullptr};
+        int64_t ld = 0;
+        int nsig = 0;
+        std::vector<int64_t> l3;
+    };
+    Entry e[2];
+    int head = 0, count = 0;
+    uint64_t next_token = 1;
+
+    bool full() const { return count >= 2; }
+    int slot(int k) const { return (head + k) & 1; }
+    // records a pass in slot(count) and returns its token (0: the ring is full)
+    uint64_t push(const float* mic, const float* ref, const float* near, int64_t ld, int nsig,
+                  const int64_t* lengths3, int32_t B) {
+        if (full()) return 0;
+        Entry& c = e[slot(count)];
+        c.sig[0] = mic; c.sig[1] = ref; c.sig[2] = near;
+        c.ld = ld;
+        c.nsig = nsig;
+        c.l3.assign(lengths3, lengths3 + (size_t)B * 3);
+        c.token = next_token++;
+        ++count;
+        return c.token;
+    }
+    // the pending entry with this token, or -1 (token 0 names none)
+    int find(uint64_t token) const {
+        for (int k = 0; token && k < count; ++k)
+            if (e[slot(k)].token == token) return k;
+        return -1;
+    }
+    // entry k was prepared for exactly these signals / ld / B / lengths
+    bool matches(int k, const float* mic, const float* ref, const float* near, int64_t ld, int nsig,
+                 const int64_t* lengths3, int32_t B) const {
+        const Entry& c = e[slot(k)];
+        return c.sig[0] == mic && c.sig[1] == ref && c.sig[2] == near && c.ld == ld && c.nsig == nsig &&
+               c.l3.size() == (size_t)B * 3 && std::memcmp(c.l3.data(), lengths3, (size_t)B * 3 * sizeof(int64_t)) == 0;
+    }
+    // drops the k entries queued before entry k, and entry k itself
+    void consume(int k) {
+        for (int i = 0; i <= k; ++i) e[slot(i)].token = 0;
+        head = slot(k + 1);
+        count -= k + 1;
+    }
+};
+
+}  // namespace aec

@@ -4,24 +4,17 @@
 #include <stdint.h>
 
 #include "aec_fft.h"
+#include "aec_host.h"
 #include "aec_knobs.h"
 
 namespace aec {
 
-constexpr int kFPB = 16;            // frames per analysis / synthesis block (16 groups x 16 lanes)
-constexpr int kHopsOut = kFPB - 1;  // output hops per synthesis block
+// kFPB, kHopsOut, kPipeTaps and WorkItem: aec_host.h (the host's work-list builder and call plan use them)
 constexpr int kCH = 16;             // frames per chunk in the GRU pipeline
 constexpr int kMomChunks = 8;       // moment partials per (stream, signal)
 
 constexpr int kAnalysisBlocksPerCU = 3;
 constexpr int kWeights = 12544;     // Little_net parameter blob (state_dict order, include/aec_hip.h)
-
-// One analysis work item: 4 consecutive frames [wt, wt+4) of stream b (length n).
-struct WorkItem {
-    int32_t b;
-    int32_t wt;
-    int64_t n;
-};
 
 struct AnalysisArgs {
     const float* sig[3];
@@ -166,8 +159,9 @@ hipError_t launch_mic_erb(const float2* spec, float* feats, const int64_t* lens,
 hipError_t launch_gru(const GruArgs& a, int B, hipStream_t st);
 hipError_t launch_synthesis(const SynthArgs& a, hipStream_t st);
 hipError_t launch_stream_step(const StreamStepArgs& a, int B, int taps, hipStream_t st);
-// K3+K4 fused (aec_gru_synth.hip): GRU + head + synthesis of the NLMS error spectrum
-hipError_t launch_gru_synth(const GruArgs& g, const SynthArgs& y, int B, hipStream_t st);
+// K3+K4 fused (aec_gru_synth.hip): GRU + head + synthesis of the NLMS error spectrum, one stream per
+// block or two (Plan::gru_one, aec_host.h)
+hipError_t launch_gru_synth(const GruArgs& g, const SynthArgs& y, int B, bool one_per_block, hipStream_t st);
 // Small-batch pipeline: the split path's NLMS recursion and mic_erb run in producer blocks of the
 // GRU + synthesis launch (gru_synth_kernel<1, true>), chunk by chunk ahead of the recurrence
 struct PipeArgs {
@@ -183,7 +177,6 @@ struct PipeArgs {
     int spin_limit;                   // polls (s_sleep 1 each) before giving up
     int stall;                        // test hook (AEC_SMALLB_PIPE_STALL): producers never publish
 };
-constexpr int kPipeTaps = 4;          // the one tap count the pipeline is instantiated for
 hipError_t launch_gru_synth_pipe(const GruArgs& g, const SynthArgs& y, const PipeArgs& q, int B, hipStream_t st);
 size_t gru_synth_smem_bytes();
 

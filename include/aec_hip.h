@@ -131,7 +131,9 @@ aec_status aec_prepare(aec_handle* h, const float* mic, const float* ref, const 
 /* aec_process_siglens taking the look-ahead `token` names: the pending
  * look-aheads queued before it are dropped, and the call fails
  * (AEC_ERR_INVALID_ARG, nothing launched) when the token is not pending or was
- * prepared for other signal pointers, ld, B or lengths. */
+ * prepared for other signal pointers, ld, B or lengths.  A call that fails with
+ * nothing launched (an allocation, an earlier call's reported time-out)
+ * consumes nothing: the token and the look-aheads before it stay pending. */
 aec_status aec_process_prepared(aec_handle* h, uint64_t token, const float* mic, const float* ref, const float* near,
                                 const int64_t* lengths3, int32_t B, int64_t ld, float* out, int64_t ld_out,
                                 float* loss, void* stream);

@@ -41,7 +41,7 @@ lib = _lib.load()
 buf = np.zeros((2, 12, 96, 2), np.uint64)
 rc = lib.aec_debug_gru_tick_prof(buf.ctypes.data_as(ctypes.c_void_p), ctypes.c_size_t(buf.nbytes))
 assert rc == 0, rc
-ns = int(os.environ.get('AEC_GRU_NS', '0')) or (1 if 2 * B <= 256 else 2)     # launch_gru_synth's rule
+ns = int(os.environ.get('AEC_GRU_NS', '0')) or (1 if 2 * B <= 256 else 2)     # plan_call's rule (csrc/aec_host.h)
 roles = ['rec'] * ns + ['gi'] * 3 + ['head'] * 3 + ['synth'] * 4
 nticks = (n // 256 + 1 + 16 // ns - 1) // (16 // ns) + 6
 for blk in range(2 if B > 64 * ns else 1):
