@@ -23,7 +23,8 @@ AEC_ERR_UNSUPPORTED = 4
 _STATUS = {0: 'AEC_OK', 1: 'AEC_ERR_INVALID_ARG', 2: 'AEC_ERR_OOM', 3: 'AEC_ERR_HIP', 4: 'AEC_ERR_UNSUPPORTED'}
 
 # every symbol include/aec_hip.h declares
-EXPORTS = ('aec_weights_count', 'aec_create', 'aec_set_weights', 'aec_set_erb', 'aec_process', 'aec_process_siglens',
+EXPORTS = ('aec_weights_count', 'aec_create', 'aec_set_weights', 'aec_set_erb', 'aec_set_canceller', 'aec_process',
+           'aec_process_siglens',
            'aec_prepare', 'aec_prepare_siglens', 'aec_process_prepared',
            'aec_stream_open', 'aec_stream_reset', 'aec_stream_step',
            'aec_set_debug', 'aec_debug_copy', 'aec_profile_enable', 'aec_profile_read',
@@ -79,6 +80,9 @@ def load():
     lib.aec_set_weights.restype = ctypes.c_int
     lib.aec_set_erb.argtypes = [P, P]
     lib.aec_set_erb.restype = ctypes.c_int
+    if LIB_PATH == _DEFAULT_LIB or hasattr(lib, 'aec_set_canceller'):
+        lib.aec_set_canceller.argtypes = [P, ctypes.c_int32, ctypes.c_float, ctypes.c_float]
+        lib.aec_set_canceller.restype = ctypes.c_int
     lib.aec_process.argtypes = [P, P, P, P, P, ctypes.c_int32, ctypes.c_int64, P, ctypes.c_int64, P, P]
     lib.aec_process.restype = ctypes.c_int
     lib.aec_process_siglens.argtypes = [P, P, P, P, P, ctypes.c_int32, ctypes.c_int64, P, ctypes.c_int64, P, P]
@@ -235,6 +239,11 @@ class Handle:
             raise ValueError(f'erb must be [257, 32], got {tuple(erb.shape)}')
         check(self.lib.aec_set_erb(self.h, erb.ctypes.data), self.h, 'aec_set_erb')
 
+    def set_canceller(self, kind, a=1.0, p0=0.0):
+        """kind: 'nlms' / 0 or 'kalman' / 1 (aec_set_canceller)."""
+        kind = {'nlms': 0, 'kalman': 1}.get(kind, kind)
+        check(self.lib.aec_set_canceller(self.h, int(kind), float(a), float(p0)), self.h, 'aec_set_canceller')
+
     def set_debug(self, on: bool):
         check(self.lib.aec_set_debug(self.h, int(bool(on))), self.h, 'aec_set_debug')
 
@@ -343,6 +352,8 @@ def crn_config(version, conf, dtype, nlms=None):
     c.use_cbn = int(bool(conf.get('use_cbn', False)))
     c.masking_mode = ord(conf.get('masking_mode', 'C')[0]) if version == 2 else ord('C')
     c.dtype = {'f32': 0, 'float32': 0, 'bf16': 1, 'bfloat16': 1, 'fp8': 2, 'mxfp8': 2}[dtype]
+    if nlms and nlms.get('kind', 'nlms') != 'nlms':
+        raise NotImplementedError(f"the CRN front end runs the FD-NLMS only, not kind={nlms['kind']!r}")
     if nlms:
         c.nlms_taps = int(nlms.get('taps', 4))
         c.nlms_mu = float(nlms.get('mu', 0.3))

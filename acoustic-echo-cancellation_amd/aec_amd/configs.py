@@ -56,3 +56,15 @@ nlms_conf = {
     'beta': 0.5,
     'delta': 1e-4,
 }
+
+# Build-defined frequency-domain Kalman canceller defaults (no reference
+# counterpart; include/aec_hip.h aec_set_canceller): 'kind' selects it, a is
+# the echo-path transition factor, p0 the initial tap covariance; no step size.
+kalman_conf = {
+    'kind': 'kalman',
+    'taps': 4,
+    'a': 0.999,
+    'beta': 0.5,
+    'delta': 1e-4,
+    'p0': 1.0,
+}

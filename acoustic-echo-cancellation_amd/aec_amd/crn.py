@@ -114,6 +114,9 @@ class _DCCRNBase(nn.Module):
         self.config = config
         self.dtype_name = dtype
         self.nlms = dict(nlms) if nlms else None   # build-defined FD-NLMS front end (include/aec_crn.h)
+        if self.nlms and self.nlms.get('kind', 'nlms') != 'nlms':
+            raise NotImplementedError(f"the CRN front end runs the FD-NLMS only, not kind={self.nlms['kind']!r}: "
+                                      "the Kalman canceller is Little_net's (configs.kalman_conf)")
         self._handles = {}
         self._p_key = {}
         self._last_shape = {}                      # device index -> (B, Tmax) of the last forward

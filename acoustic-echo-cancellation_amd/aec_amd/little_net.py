@@ -180,6 +180,11 @@ class Little_net(nn.Module):
             nl = self.nlms or {}
             h = _lib.Handle(idx, nlms_taps=nl.get('taps', 0), nlms_mu=nl.get('mu', 0.5),
                             nlms_beta=nl.get('beta', 0.9), nlms_delta=nl.get('delta', 1e-4))
+            kind = nl.get('kind', 'nlms')
+            if kind == 'kalman':
+                h.set_canceller('kalman', nl.get('a', 0.999), nl.get('p0', 1.0))
+            elif kind != 'nlms':
+                raise ValueError(f"nlms['kind'] must be 'nlms' or 'kalman', got {kind!r}")
             self._handles[idx] = h
         if not upload:
             return h, idx

@@ -27,6 +27,8 @@ writes every file.
 
 Extra flags (all optional):
 - `--nlms` puts the FD-NLMS stage in front of the post-filter;
+- `--kalman` puts the frequency-domain Kalman canceller there instead
+  (`configs.kalman_conf`; the two flags exclude each other);
 - `--streams` sets the utterances per GPU call;
 - `--device` picks the GPU (default: LOCAL_RANK, the rank's bound GPU);
 - `--gather` writes every file on rank 0 (waveforms gathered over RCCL).
@@ -44,7 +46,7 @@ from typing import Callable, List, Optional, Sequence
 import numpy as np
 
 from . import h5lite, shard, wavio
-from .configs import erb_conf, nlms_conf, speech_conf
+from .configs import erb_conf, kalman_conf, nlms_conf, speech_conf
 
 # enhance(mic, ref, near, lengths[B][3] = (mic, ref, near) lengths) -> list of
 # 1-D float32 outputs, one per row, each 256*(n_mic//256) samples
@@ -73,7 +75,10 @@ def build_parser():
     p.add_argument('--est_path', type=str, default='/data/lihaoming/datasets/synthetic/estimate',
                    help='Path to dump estimates')
     # gfx950 extras
-    p.add_argument('--nlms', action='store_true', help='FD-NLMS linear AEC in front of the post-filter')
+    lin = p.add_mutually_exclusive_group()
+    lin.add_argument('--nlms', action='store_true', help='FD-NLMS linear AEC in front of the post-filter')
+    lin.add_argument('--kalman', action='store_true',
+                     help='frequency-domain Kalman linear AEC in front of the post-filter')
     p.add_argument('--streams', type=int, default=64, help='utterances per GPU call')
     p.add_argument('--device', type=int, default=None, help='GPU index (default: LOCAL_RANK or 0)')
     p.add_argument('--gather', action='store_true',
@@ -114,7 +119,8 @@ class Tester(object):
         from .little_net import Little_net
         local = self.args.device if self.args.device is not None else shard.local_rank()
         device = torch.device('cuda', local)
-        net = Little_net(speech_conf, erb_conf['total_erb_bands'], nlms=nlms_conf if self.args.nlms else None)
+        lin = kalman_conf if getattr(self.args, 'kalman', False) else (nlms_conf if self.args.nlms else None)
+        net = Little_net(speech_conf, erb_conf['total_erb_bands'], nlms=lin)
         logger.info('backbone summary:\n{}'.format(net))
         param_count = sum(int(np.prod(p.shape)) for p in net.parameters())
         logger.info('Trainable parameter count: {:,d} -> {:.2f} MB\n'.format(param_count,

@@ -117,12 +117,15 @@ __device__ __forceinline__ v2f vrot(v2f a) { return v2f{-a.y, a.x}; }       // i
 // ops; the recursion's waves share their SIMDs with the transforms.
 template <int TAPS>
 struct NlmsBin {
+    // K2n's A/B option of running the mic_erb pass on the recursion's waves (erb_role 2) exists for this bin
+    static constexpr bool kErbOnNlmsWaves = true;
     float2 w[TAPS];
     float p1[TAPS], p2[TAPS], p4[TAPS];   // operands of R[t], R[t-1], ...
     float qx[TAPS], qy[TAPS];             // per-half |R|^2 of the same entries
     float2 p;                             // smoothed power per half
     bool dual;
-    __device__ __forceinline__ void reset(bool dual_) {
+    // p0: the Kalman canceller's initial covariance (KalmanBin::reset), unused here
+    __device__ __forceinline__ void reset(bool dual_, float /*p0*/ = 0.f) {
         dual = dual_;
 #pragma unroll
         for (int l = 0; l < TAPS; ++l) {
@@ -178,6 +181,105 @@ struct NlmsBin {
         for (int l = 0; l < TAPS; ++l) {
             w[l].x = fmaf(gx, p1[l], fmaf(-gy, p2[l], w[l].x));
             w[l].y = fmaf(gy, p4[l], fmaf(gx, p2[l], w[l].y));
+        }
+        return make_float2(ex, ey);
+    }
+};
+
+// One lane's frequency-domain Kalman canceller (the diagonalised partitioned
+// FD Kalman filter of Enzner & Vary / Kuech et al., process noise from the tap
+// energy), with NlmsBin's interface and lane layout: one complex
+// bin, or on the slot-0 lane the real bins 0 and 256 in the x / y halves.  Per
+// bin, with R_l = R[t-l]:
+//   E    = D - sum_l W[l] R_l
+//   psi  = beta psi + (1 - beta) |E|^2
+//   S    = sum_l P[l] |R_l|^2 + psi + delta,   G_l = P[l] / S
+//   W[l] = a (W[l] + G_l conj(R_l) E)
+//   P[l] = a^2 (1 - G_l |R_l|^2) P[l] + (1 - a^2) |W[l]|^2
+// step()'s `a` takes the place of NlmsBin's mu.  Covariance, error power and S
+// are kept per half (pp[l].x / .y, p.x / .y): the dual lane's two real bins
+// need their own, and a complex lane computes the same value in both halves
+// (|E|^2 and |W|^2 are formed once and selected into the halves), so every
+// lane runs one instruction stream.  Registers (K2n holds the state beside 64
+// VGPRs of dd / rr staging, and 168 is the 3-waves-per-SIMD limit): the
+// covariances take the place of NlmsBin's qx / qy, 7 VGPRs per tap as there.
+// |R_l|^2 never exists on its own: the products P[l] |R_l|^2 are formed as
+// (P p1) p1 + (P p2) p2, which change with P every frame, so the unrolled
+// frame loops have nothing to carry from the frame R entered to the frame it
+// leaves.  One v_rcp_f32 per half and frame; no other division.
+template <int TAPS>
+struct KalmanBin {
+    static constexpr bool kErbOnNlmsWaves = false;   // erb_role 2 runs as 1: its loop invariants cost <8> its fit
+    float2 w[TAPS];
+    float p1[TAPS], p2[TAPS], p4[TAPS];   // operands of R[t], R[t-1], ... (NlmsBin's)
+    float2 pp[TAPS];                      // tap covariance P[l] per half
+    float2 p;                             // error power psi per half
+    bool dual;
+    __device__ __forceinline__ void reset(bool dual_, float p0) {
+        dual = dual_;
+#pragma unroll
+        for (int l = 0; l < TAPS; ++l) {
+            w[l] = make_float2(0.f, 0.f);
+            p1[l] = p2[l] = p4[l] = 0.f;
+            pp[l] = make_float2(p0, p0);
+        }
+        p = make_float2(0.f, 0.f);
+    }
+    __device__ __forceinline__ void hist(int l, float2 r) {
+        p1[l] = r.x;
+        p2[l] = dual ? 0.f : -r.y;
+        p4[l] = dual ? r.y : r.x;
+    }
+    // P[l] |R_l|^2 per half
+    __device__ __forceinline__ float2 pq(int l) const {
+        return make_float2(fmaf(pp[l].x * p1[l], p1[l], (pp[l].x * p2[l]) * p2[l]),
+                           fmaf(pp[l].y * p4[l], p4[l], (pp[l].y * p2[l]) * p2[l]));
+    }
+    // One frame: returns E = D - sum_l W[l] R[t-l] and adapts W, P, psi.
+    __device__ __forceinline__ float2 step(float2 d, float2 r, float a, float beta, float delta) {
+#pragma unroll
+        for (int l = TAPS - 1; l >= 1; --l) {
+            p1[l] = p1[l - 1];
+            p2[l] = p2[l - 1];
+            p4[l] = p4[l - 1];
+        }
+        hist(0, r);
+        // y and sum_l P[l] |R_l|^2: two partial chains per half, as NlmsBin's y
+        constexpr int H = (TAPS + 1) / 2;
+        float2 t[TAPS];
+        float yx[2], yy[2], sx[2], sy[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int l0 = h ? H : 0, l1 = h ? TAPS : H;
+            yx[h] = yy[h] = sx[h] = sy[h] = 0.f;
+#pragma unroll
+            for (int l = l0; l < l1; ++l) {
+                yx[h] = fmaf(w[l].x, p1[l], fmaf(w[l].y, p2[l], yx[h]));
+                yy[h] = fmaf(w[l].y, p4[l], fmaf(-w[l].x, p2[l], yy[h]));
+                t[l] = pq(l);
+                sx[h] += t[l].x;
+                sy[h] += t[l].y;
+            }
+        }
+        const float ex = d.x - (yx[0] + yx[1]);
+        const float ey = d.y - (yy[0] + yy[1]);
+        const float exx = ex * ex, eyy = ey * ey, e2 = fmaf(ex, ex, eyy);
+        p.x = fmaf(beta, p.x, (1.f - beta) * (dual ? exx : e2));
+        p.y = fmaf(beta, p.y, (1.f - beta) * (dual ? eyy : e2));
+        const float ix = __builtin_amdgcn_rcpf((sx[0] + sx[1]) + (p.x + delta));
+        const float iy = __builtin_amdgcn_rcpf((sy[0] + sy[1]) + (p.y + delta));
+        const float a2 = a * a, b2 = 1.f - a2;
+#pragma unroll
+        for (int l = 0; l < TAPS; ++l) {
+            const float gx = pp[l].x * ix, gy = pp[l].y * iy;      // G_l
+            const float ux = fmaf(ex, p1[l], -ey * p2[l]);         // (conj(R_l) E).x
+            const float uy = fmaf(ey, p4[l], ex * p2[l]);          // (conj(R_l) E).y
+            w[l].x = a * fmaf(gx, ux, w[l].x);
+            w[l].y = a * fmaf(gy, uy, w[l].y);
+            const float wxx = w[l].x * w[l].x, wyy = w[l].y * w[l].y, w2 = fmaf(w[l].x, w[l].x, wyy);
+            // a^2 (1 - G_l |R_l|^2) P[l] = a^2 (P[l] - (P[l] |R_l|^2 / S) P[l])
+            pp[l].x = fmaf(b2, dual ? wxx : w2, a2 * fmaf(-(t[l].x * ix), pp[l].x, pp[l].x));
+            pp[l].y = fmaf(b2, dual ? wyy : w2, a2 * fmaf(-(t[l].y * iy), pp[l].y, pp[l].y));
         }
         return make_float2(ex, ey);
     }

@@ -21,6 +21,12 @@ constexpr int kHopsOut = kFPB - 1;  // output hops per synthesis block
 constexpr int kPipeTaps = 4;        // the one tap count the small-batch pipeline is instantiated for
 
 inline int64_t num_frames(int64_t n) { return n / 256 + 1; }
+// Floats of one stream's state (aec_stream_*; layout in aec_launch.h): 1024, then one row of 256
+// float2 per canceller field: 2 taps for the NLMS, taps + 1 more (covariances, error power) for
+// the Kalman canceller
+inline int64_t stream_state_floats(int taps, int kalman = 0) {
+    return 1024 + (int64_t)1024 * taps + (kalman ? (int64_t)512 * (taps + 1) : 0);
+}
 inline int64_t out_len(int64_t n) { return 256 * (n / 256); }
 
 // ---------------------------------------------------------------------------
@@ -314,6 +320,7 @@ struct PlanIn {
     int num_cus;
     int gru_ns;         // AEC_GRU_NS as read for this call: 0 by the batch size, 1 / 2 forced
     bool lookahead;     // the call consumes a look-ahead normaliser pass
+    int kalman = 0;     // the canceller is the Kalman filter (aec_set_canceller): the pipeline is not built for it
 };
 struct Plan {
     bool nlms_batch;    // K2n: one block per stream runs transforms + recursion
@@ -332,7 +339,7 @@ inline Plan plan_call(const PlanIn& in) {
     Plan p;
     p.nlms_batch = in.nlms_taps > 0 && !small;
     p.split = in.nlms_taps > 0 && small;
-    p.pipe = in.small_pipe && in.nlms_taps == kPipeTaps && small && fused && half && in.gru_ns != 2;
+    p.pipe = in.small_pipe && in.nlms_taps == kPipeTaps && !in.kalman && small && fused && half && in.gru_ns != 2;
     p.bypass_fused = in.nlms_taps == 0 && fused && half;
     p.fold_norm = (p.split || p.bypass_fused) && !in.lookahead;
     p.gru_one = in.gru_ns == 1 || (in.gru_ns != 2 && 2 * (int64_t)in.B <= (int64_t)std::max(in.num_cus, 2));

@@ -375,7 +375,10 @@ __device__ __forceinline__ void nlms_transform(float* wr, float* scr, float4 (&p
     rfft_unpack(v, lb, sTw512, xa, xb, x128);
 }
 
-template <int TAPS>
+// BIN: the canceller's bin type, NlmsBin<TAPS> or KalmanBin<TAPS> (aec_frame.h; for the latter p.mu
+// carries the transition factor a): the instantiations differ in the recursion's arithmetic and
+// registers only.
+template <class BIN>
 __global__ __launch_bounds__(kNlmsWaves * 64, 1) void nlms_analysis_kernel(NlmsArgs p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x;
@@ -441,7 +444,7 @@ __global__ __launch_bounds__(kNlmsWaves * 64, 1) void nlms_analysis_kernel(NlmsA
     // waves (erb_role 0: their near transform is gone, so the pass leaves the
     // ref waves and the two transform roles carry one transform and one ERB
     // projection pass each)
-    const int erb_role = p.erb_role == 2 ? 2 : (p.erb_role == 0 && !have_near ? 0 : 1);
+    const int erb_role = BIN::kErbOnNlmsWaves && p.erb_role == 2 ? 2 : (p.erb_role == 0 && !have_near ? 0 : 1);
     auto mic_erb_pass = [&](int c2) {
         const int64_t t2 = (int64_t)c2 * kFPB + 4 * q + gg;
         float* er = sE + (c2 & 1) * kFPB * kNRow + (4 * q + gg) * kNRow;
@@ -473,8 +476,8 @@ __global__ __launch_bounds__(kNlmsWaves * 64, 1) void nlms_analysis_kernel(NlmsA
     // state and the transforms' working set in disjoint regions.
     if (role == 2) {
         const int k = lane + 64 * q;                                  // bin k; k = 0 also bin 256
-        NlmsBin<TAPS> st;
-        st.reset(k == 0);
+        BIN st;
+        st.reset(k == 0, p.p0);
         float2 dd[kFPB], rr[kFPB];
         for (int c = 0; c < nch + 2; ++c) {
             TICK_STAMP(0);
@@ -511,7 +514,8 @@ __global__ __launch_bounds__(kNlmsWaves * 64, 1) void nlms_analysis_kernel(NlmsA
                     }
                 }
             }
-            if (erb_role == 2 && c >= 2 && !(p.mode & 4)) mic_erb_pass(c - 2);
+            if constexpr (BIN::kErbOnNlmsWaves)
+                if (erb_role == 2 && c >= 2 && !(p.mode & 4)) mic_erb_pass(c - 2);
             TICK_STAMP(1);
             __syncthreads();                                          // rows of chunk c complete
             TICK_STAMP(2);
@@ -719,17 +723,18 @@ __global__ __launch_bounds__(256) void synthesis_kernel(SynthArgs p) {
 // --------------------------------------------------------------------------
 constexpr int kRecP = 8;
 
-template <int TAPS>
+template <class BIN>
 __global__ __launch_bounds__(256) void nlms_recursion_kernel(const float2* __restrict__ rows, float2* __restrict__ spec,
                                                              const int64_t* __restrict__ lens, int64_t Tmax, float mu,
-                                                             float beta, float delta, int b0, float2* dummy_rows) {
+                                                             float beta, float delta, int b0, float2* dummy_rows,
+                                                             float p0) {
     const int b = b0 + blockIdx.x;
     const int64_t T = lens[b] / kHop + 1;
     const int k = threadIdx.x;
     const float2* r0 = rows + (int64_t)b * Tmax * 512;
     float2* e0 = spec + (int64_t)b * Tmax * kSpecRow;
-    NlmsBin<TAPS> st;
-    st.reset(k == 0);
+    BIN st;
+    st.reset(k == 0, p0);
     float2 dd[kRecP], rr[kRecP];
     auto fetch = [&](int64_t t, int i) {                  // rows past the end: any valid row (results unused)
         const int64_t tc = t < T ? t : T - 1;
@@ -784,9 +789,25 @@ hipError_t launch_nlms_recursion(const float2* rows, float2* spec, const int64_t
                                  float mu, float beta, float delta, int b0, int nb, float2* dummy_rows, hipStream_t st) {
     if (nb <= 0) return hipSuccess;
     switch (taps) {
-#define AEC_REC_CASE(T)                                                                                       \
-        case T: hipLaunchKernelGGL(nlms_recursion_kernel<T>, dim3(nb), dim3(256), 0, st, rows, spec, lens, Tmax, mu, \
-                                   beta, delta, b0, dummy_rows); break;
+#define AEC_REC_CASE(T)                                                                                          \
+        case T: hipLaunchKernelGGL(nlms_recursion_kernel<NlmsBin<T>>, dim3(nb), dim3(256), 0, st, rows, spec, lens, \
+                                   Tmax, mu, beta, delta, b0, dummy_rows, 0.f); break;
+        AEC_REC_CASE(1) AEC_REC_CASE(2) AEC_REC_CASE(3) AEC_REC_CASE(4)
+        AEC_REC_CASE(5) AEC_REC_CASE(6) AEC_REC_CASE(7) AEC_REC_CASE(8)
+#undef AEC_REC_CASE
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_kalman_recursion(const float2* rows, float2* spec, const int64_t* lens, int64_t Tmax, int taps,
+                                   float a, float beta, float delta, float p0, int b0, int nb, float2* dummy_rows,
+                                   hipStream_t st) {
+    if (nb <= 0) return hipSuccess;
+    switch (taps) {
+#define AEC_REC_CASE(T)                                                                                            \
+        case T: hipLaunchKernelGGL(nlms_recursion_kernel<KalmanBin<T>>, dim3(nb), dim3(256), 0, st, rows, spec, lens, \
+                                   Tmax, a, beta, delta, b0, dummy_rows, p0); break;
         AEC_REC_CASE(1) AEC_REC_CASE(2) AEC_REC_CASE(3) AEC_REC_CASE(4)
         AEC_REC_CASE(5) AEC_REC_CASE(6) AEC_REC_CASE(7) AEC_REC_CASE(8)
 #undef AEC_REC_CASE
@@ -856,28 +877,41 @@ hipError_t launch_synthesis(const SynthArgs& a, hipStream_t st) {
     return hipGetLastError();
 }
 
-template <int TAPS>
+template <class BIN>
 static hipError_t launch_nlms_t(const NlmsArgs& a, int nb, hipStream_t st) {
     // > 64 KiB of LDS: opt in once per instantiation
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(nlms_analysis_kernel<TAPS>),
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(nlms_analysis_kernel<BIN>),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL(nlms_analysis_kernel<TAPS>, dim3(nb), dim3(kNlmsWaves * 64), nlms_smem_bytes(a.sched_len, TAPS),
+    hipLaunchKernelGGL(nlms_analysis_kernel<BIN>, dim3(nb), dim3(kNlmsWaves * 64), nlms_smem_bytes(a.sched_len, a.taps),
                        st, a);
     return hipGetLastError();
 }
 
 hipError_t launch_nlms_analysis(const NlmsArgs& a, int nb, hipStream_t st) {
     if (nb <= 0) return hipSuccess;
+    if (a.kalman) {
+        switch (a.taps) {
+            case 1: return launch_nlms_t<KalmanBin<1>>(a, nb, st);
+            case 2: return launch_nlms_t<KalmanBin<2>>(a, nb, st);
+            case 3: return launch_nlms_t<KalmanBin<3>>(a, nb, st);
+            case 4: return launch_nlms_t<KalmanBin<4>>(a, nb, st);
+            case 5: return launch_nlms_t<KalmanBin<5>>(a, nb, st);
+            case 6: return launch_nlms_t<KalmanBin<6>>(a, nb, st);
+            case 7: return launch_nlms_t<KalmanBin<7>>(a, nb, st);
+            case 8: return launch_nlms_t<KalmanBin<8>>(a, nb, st);
+            default: return hipErrorInvalidValue;
+        }
+    }
     switch (a.taps) {
-        case 1: return launch_nlms_t<1>(a, nb, st);
-        case 2: return launch_nlms_t<2>(a, nb, st);
-        case 3: return launch_nlms_t<3>(a, nb, st);
-        case 4: return launch_nlms_t<4>(a, nb, st);
-        case 5: return launch_nlms_t<5>(a, nb, st);
-        case 6: return launch_nlms_t<6>(a, nb, st);
-        case 7: return launch_nlms_t<7>(a, nb, st);
-        case 8: return launch_nlms_t<8>(a, nb, st);
+        case 1: return launch_nlms_t<NlmsBin<1>>(a, nb, st);
+        case 2: return launch_nlms_t<NlmsBin<2>>(a, nb, st);
+        case 3: return launch_nlms_t<NlmsBin<3>>(a, nb, st);
+        case 4: return launch_nlms_t<NlmsBin<4>>(a, nb, st);
+        case 5: return launch_nlms_t<NlmsBin<5>>(a, nb, st);
+        case 6: return launch_nlms_t<NlmsBin<6>>(a, nb, st);
+        case 7: return launch_nlms_t<NlmsBin<7>>(a, nb, st);
+        case 8: return launch_nlms_t<NlmsBin<8>>(a, nb, st);
         default: return hipErrorInvalidValue;
     }
 }

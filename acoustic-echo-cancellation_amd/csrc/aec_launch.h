@@ -58,6 +58,8 @@ struct NlmsArgs {
     int mode;                // timing experiments only (AEC_NLMS_MODE): bit0 skip recursion,
                              // bit1 skip near transform, bit2 skip mic ERB, bit3 skip mic/ref transforms;
                              // bit4 (valid results): the ref waves' two ERB projections in two passes
+    int kalman;              // 1: the Kalman canceller (nlms_analysis_kernel<KalmanBin<taps>>): mu carries its
+    float p0;                //    transition factor a, p0 the initial tap covariance
 };
 
 struct GruArgs {
@@ -96,17 +98,18 @@ struct SynthArgs {
 };
 
 // Fused streaming step (aec_stream.hip): one 256-sample hop of B streams.
-// Per-stream state, floats (stride = stream_state_floats(taps)):
+// Per-stream state, floats (stride = stream_state_floats(taps, kalman), aec_host.h):
 //   [0, 512)     previous input hop: mic (256), ref (256)
 //   [512, 768)   OLA tail: second half of the previous synthesis frame
 //   [768, 800)   GRU h
-//   [1024, ...)  NLMS, float2[2*taps][256] by field: w[0..taps-1],
-//                far-end history r[t-1 .. t-taps+1], power p
+//   [1024, ...)  canceller, rows of float2[256] by field: w[0..taps-1],
+//                far-end history r[t-1 .. t-taps+1], NLMS power p (row 2 taps - 1,
+//                unused by the Kalman canceller); Kalman: tap covariances
+//                P[0..taps-1] (rows 2 taps ..), error power psi (row 3 taps)
 constexpr int kStPrev = 0;
 constexpr int kStTail = 512;
 constexpr int kStH = 768;
 constexpr int kStNlms = 1024;
-inline int64_t stream_state_floats(int taps) { return 1024 + (int64_t)1024 * taps; }
 
 struct StreamStepArgs {
     const float* mic;        // [B][ld_in] hop k of every stream
@@ -122,6 +125,8 @@ struct StreamStepArgs {
     int sched_len;
     const float* bintab;
     float mu, beta, delta;
+    int kalman;              // 1: the Kalman canceller: mu carries its transition factor a,
+    float p0;                //    p0 the initial tap covariance
 };
 
 // dynamic LDS bytes (must match the carve in the kernels)
@@ -154,11 +159,16 @@ hipError_t launch_nlms_analysis(const NlmsArgs& a, int nb, hipStream_t st);
 // the mic_erb pass over all frames
 hipError_t launch_nlms_recursion(const float2* rows, float2* spec, const int64_t* lens, int64_t Tmax, int taps,
                                  float mu, float beta, float delta, int b0, int nb, float2* dummy_rows, hipStream_t st);
+hipError_t launch_kalman_recursion(const float2* rows, float2* spec, const int64_t* lens, int64_t Tmax, int taps,
+                                   float a, float beta, float delta, float p0, int b0, int nb, float2* dummy_rows,
+                                   hipStream_t st);
 hipError_t launch_mic_erb(const float2* spec, float* feats, const int64_t* lens, int64_t Tmax, const float* sched,
                           int sched_len, const WorkItem* items, int64_t nitems, hipStream_t st);
 hipError_t launch_gru(const GruArgs& a, int B, hipStream_t st);
 hipError_t launch_synthesis(const SynthArgs& a, hipStream_t st);
 hipError_t launch_stream_step(const StreamStepArgs& a, int B, int taps, hipStream_t st);
+hipError_t launch_stream_cov_fill(float* state, int64_t stride, int first, int count, int taps, float p0,
+                                  hipStream_t st);
 // K3+K4 fused (aec_gru_synth.hip): GRU + head + synthesis of the NLMS error spectrum, one stream per
 // block or two (Plan::gru_one, aec_host.h)
 hipError_t launch_gru_synth(const GruArgs& g, const SynthArgs& y, int B, bool one_per_block, hipStream_t st);

@@ -16,12 +16,14 @@
 // normalised (or raw; serving callers use their own offset).
 //
 // One block of 4 waves per stream; per-stream state lives in HBM between
-// calls (prev hop, NLMS taps / far-end history / power, GRU h, OLA tail) and
-// is read once and written once per hop.  The arithmetic is the batch path's
+// calls (prev hop, canceller taps / far-end history / power or covariances,
+// GRU h, OLA tail) and is read once and written once per hop.  The arithmetic is the batch path's
 // own (the aec_frame.h helpers, GRU step and head included), so a streamed
 // utterance reproduces aec_process bit for bit (tests/test_gpu_stream.py).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "aec_fft.h"
 #include "aec_frame.h"
@@ -34,7 +36,8 @@ namespace aec {
 constexpr int kStreamThreads = 256;
 constexpr int kSchedMax = 48;                 // ErbTables: L <= 48
 
-template <int TAPS>
+// KALMAN: the canceller is KalmanBin (p.mu carries its transition factor a), else NlmsBin
+template <int TAPS, bool KALMAN = false>
 __global__ __launch_bounds__(kStreamThreads) void stream_step_kernel(StreamStepArgs p) {
     __shared__ __attribute__((aligned(16))) float4 sSched[kSchedMax * 16];
     __shared__ int2 sComb[32];
@@ -105,11 +108,11 @@ __global__ __launch_bounds__(kStreamThreads) void stream_step_kernel(StreamStepA
 
     // NLMS bin slot k = tid (slot 0: the real pair (0, 256)); taps, power and
     // the raw far-end history r[t-1 .. t-TAPS+1] from the state
-    NlmsBin<TAPS ? TAPS : 1> nb;
+    std::conditional_t<KALMAN, KalmanBin<TAPS ? TAPS : 1>, NlmsBin<TAPS ? TAPS : 1>> nb;
     float2 rh[TAPS > 1 ? TAPS - 1 : 1];
     float2* nst = reinterpret_cast<float2*>(st + kStNlms);
     if constexpr (TAPS > 0) {
-        nb.reset(tid == 0);
+        nb.reset(tid == 0, p.p0);
 #pragma unroll
         for (int l = 0; l < TAPS; ++l) {
             const float2 w = nst[l * 256 + tid];
@@ -122,8 +125,18 @@ __global__ __launch_bounds__(kStreamThreads) void stream_step_kernel(StreamStepA
             rh[l] = r2;
             nb.hist(l, r2);
         }
-        const float2 pp = nst[(2 * TAPS - 1) * 256 + tid];
-        nb.p = pp;
+        if constexpr (KALMAN) {
+#pragma unroll
+            for (int l = 0; l < TAPS; ++l) {
+                const float2 c = nst[(2 * TAPS + l) * 256 + tid];
+                nb.pp[l] = c;
+            }
+            const float2 psi = nst[3 * TAPS * 256 + tid];
+            nb.p = psi;
+        } else {
+            const float2 pp = nst[(2 * TAPS - 1) * 256 + tid];
+            nb.p = pp;
+        }
     }
 
     // role weights: wave 0 the recurrence (W_hh k-halves, as gru_kernel's
@@ -186,7 +199,13 @@ __global__ __launch_bounds__(kStreamThreads) void stream_step_kernel(StreamStepA
 #pragma unroll
             for (int l = 1; l + 1 < TAPS; ++l) nst[(TAPS + l) * 256 + tid] = rh[l - 1];
         }
-        nst[(2 * TAPS - 1) * 256 + tid] = nb.p;
+        if constexpr (KALMAN) {
+#pragma unroll
+            for (int l = 0; l < TAPS; ++l) nst[(2 * TAPS + l) * 256 + tid] = nb.pp[l];
+            nst[3 * TAPS * 256 + tid] = nb.p;
+        } else {
+            nst[(2 * TAPS - 1) * 256 + tid] = nb.p;
+        }
         __syncthreads();
     }
 
@@ -242,9 +261,35 @@ __global__ __launch_bounds__(kStreamThreads) void stream_step_kernel(StreamStepA
     st[kStTail + tid] = sScr[0][256 + tid];
 }
 
+// A fresh Kalman state is zero except the tap covariances P[l] = p0 (rows 2 taps .. 3 taps - 1 of
+// the canceller block): `count` streams from `first`
+__global__ __launch_bounds__(256) void stream_cov_fill_kernel(float* state, int64_t stride, int first, int taps,
+                                                              float p0) {
+    float2* nst = reinterpret_cast<float2*>(state + (int64_t)(first + blockIdx.x) * stride + kStNlms);
+    for (int l = 0; l < taps; ++l) nst[(2 * taps + l) * 256 + threadIdx.x] = make_float2(p0, p0);
+}
+
+hipError_t launch_stream_cov_fill(float* state, int64_t stride, int first, int count, int taps, float p0,
+                                  hipStream_t s) {
+    if (count <= 0 || taps <= 0) return hipSuccess;
+    hipLaunchKernelGGL(stream_cov_fill_kernel, dim3(count), dim3(256), 0, s, state, stride, first, taps, p0);
+    return hipGetLastError();
+}
+
 hipError_t launch_stream_step(const StreamStepArgs& a, int B, int taps, hipStream_t s) {
     if (B <= 0) return hipSuccess;
     if (a.sched_len > kSchedMax) return hipErrorInvalidValue;
+    if (a.kalman) {
+        switch (taps) {
+#define AEC_STREAM_CASE(T) \
+            case T: hipLaunchKernelGGL((stream_step_kernel<T, true>), dim3(B), dim3(kStreamThreads), 0, s, a); break;
+            AEC_STREAM_CASE(1) AEC_STREAM_CASE(2) AEC_STREAM_CASE(3) AEC_STREAM_CASE(4)
+            AEC_STREAM_CASE(5) AEC_STREAM_CASE(6) AEC_STREAM_CASE(7) AEC_STREAM_CASE(8)
+#undef AEC_STREAM_CASE
+            default: return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
+    }
     switch (taps) {
 #define AEC_STREAM_CASE(T) \
         case T: hipLaunchKernelGGL(stream_step_kernel<T>, dim3(B), dim3(kStreamThreads), 0, s, a); break;

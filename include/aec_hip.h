@@ -13,6 +13,10 @@
  *                 (scripts/network/ERB.py:252-334) as called at
  *                 scripts/test.py:157, with batch=1 semantics per stream
  *                 (per-stream normaliser over its true length).
+ *   aec_set_canceller
+ *        selects the build-defined linear stage's adaptive filter (no reference
+ *        counterpart): the FD-NLMS (default) or the frequency-domain Kalman
+ *        filter, in aec_process, aec_process_prepared and aec_stream_step alike.
  *   aec_debug_copy
  *        exposes the intermediates the reference computes inside forward
  *        (ERB.py:282-307) for parity tests.
@@ -78,6 +82,25 @@ aec_status aec_create(const aec_config* cfg, const float* weights, size_t n_weig
  * and the post-filter (features, gains, iSTFT) runs on E instead of the mic
  * spectrum. */
 
+/* The linear stage's adaptive filter (nlms_taps > 0): kind 0 = the FD-NLMS above
+ * (the default: a handle that never calls this behaves as one that selects it),
+ * kind 1 = the diagonalised partitioned frequency-domain Kalman filter, which
+ * replaces the fixed step mu by a per-tap covariance and a per-bin error
+ * power and so holds the echo path through double talk:
+ *   E = D - sum_l W[l] R[t-l],  psi = beta psi + (1-beta) |E|^2,
+ *   S = sum_l P[l] |R[t-l]|^2 + psi + delta,  G_l = P[l] / S,
+ *   W[l] = a (W[l] + G_l conj(R[t-l]) E),
+ *   P[l] = a^2 (1 - G_l |R[t-l]|^2) P[l] + (1 - a^2) |W[l]|^2
+ * (W = 0, P = p0, psi = 0 at each stream start).  beta and delta are the
+ * config's nlms_beta / nlms_delta; nlms_mu is ignored; a in (0, 1] is the
+ * echo-path transition factor, p0 >= 0 the initial tap covariance (p0 = 0
+ * leaves the mic spectrum unchanged).  a and p0 are ignored for kind 0.
+ * AEC_ERR_INVALID_ARG: unknown kind, a outside (0, 1], p0 negative or not
+ * finite, or a streaming state is open (aec_stream_open; its layout depends on
+ * the kind).  AEC_ERR_UNSUPPORTED: nlms_taps == 0.  Training
+ * (aec_train_forward) stays the reference network's. */
+aec_status aec_set_canceller(aec_handle* h, int32_t kind, float a, float p0);
+
 aec_status aec_set_weights(aec_handle* h, const float* weights, size_t n_weights);
 aec_status aec_set_erb(aec_handle* h, const float* erb_257xbands);
 
@@ -140,7 +163,7 @@ aec_status aec_process_prepared(aec_handle* h, uint64_t token, const float* mic,
 
 /* Streaming (serving): the reference's per-frame loop (Little_net.forward,
  * ERB.py:252-334) advanced by one 256-sample hop per stream per call, as ONE
- * fused kernel launch (frame -> rFFT -> [FD-NLMS] -> ERB -> GRU step -> head
+ * fused kernel launch (frame -> rFFT -> [FD-NLMS / Kalman] -> ERB -> GRU step -> head
  * -> gains -> irFFT -> overlap-add).  Frame t needs hops t-1 and t
  * (ConvSTFT framing, attention_ccrn.py:45-52), so step k emits output hop
  * k-1; the first step's output is the warm-up region the reference trims
@@ -148,8 +171,8 @@ aec_status aec_process_prepared(aec_handle* h, uint64_t token, const float* mic,
  * past n) reproduces aec_process's out row for that stream.  The hops must
  * already be normalised: x - mean(x)/std(x) (ERB.py:254-256) needs the whole
  * utterance, which a stream does not have; near / loss are not computed.
- *   aec_stream_open(h, B)        B concurrent streams; state zeroed
- *   aec_stream_reset(h, b, st)   zero stream b's state (-1: all streams)
+ *   aec_stream_open(h, B)        B concurrent streams; state zeroed (Kalman: P = p0)
+ *   aec_stream_reset(h, b, st)   stream b's state (-1: all streams) back to that start
  *   aec_stream_step(h, mic, ref, ld_in, out, ld_out, st)
  *        mic, ref: device [B, ld_in] float32, hop k of every stream;
  *        out: device [B, ld_out] float32 receives output hop k-1 (256 samples). */
