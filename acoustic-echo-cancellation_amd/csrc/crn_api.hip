@@ -1,11 +1,11 @@
 // crn_api.hip — the DCCRN C ABI (include/aec_crn.h) over crn_kernels.hip.
 //
-// Host side of the reference's DCCRN eval forward (Stage2_lhm/scripts/
-// network/dccrn.py:453-594, dccrn2.py:10-218): parses the state_dict-ordered
-// parameter blob, folds every eval-mode BatchNorm2d / ComplexBatchNorm into
-// its complex conv (float64), permutes weights into the kernels' layouts
-// (channels-last maps, decoder skip order, LSTM unit order and gate packing),
-// owns a grow-only workspace and sequences the launches.
+// Device side of the reference's DCCRN eval forward (Stage2_lhm/scripts/
+// network/dccrn.py:453-594, dccrn2.py:10-218): uploads the operands that
+// crn_host.h folds and packs from the parameter blob (the blob layout, the
+// float64 norm fold, the kernels' weight layouts, the MX-fp8 rows, the
+// per-layer rules and the workspace sizes all live there, GPU-free and tested
+// on the CPU), owns a grow-only workspace and sequences the launches.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,69 +21,30 @@
 #include "aec_device.h"
 #include "aec_launch.h"
 #include "aec_tables.h"
+#include "crn_host.h"
 #include "crn_launch.h"
 
 using crn::bf16_t;
+using namespace crn_host;
 
 namespace {
 
-int ilog2(int64_t v) {
-    int r = 0;
-    while ((1ll << r) < v) ++r;
-    return (1ll << r) == v ? r : -1;
-}
-
-uint16_t host_f2bf(float f) {
-    uint32_t u;
-    std::memcpy(&u, &f, 4);
-    if ((u & 0x7F800000u) == 0x7F800000u) return (uint16_t)(u >> 16) | ((u & 0xFFFF) ? 0x40 : 0);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-
-struct Cursor {
-    const float* p;
-    size_t n, off = 0;
-    bool ok = true;
-    const float* take(size_t k) {
-        if (off + k > n) {
-            ok = false;
-            return nullptr;
-        }
-        const float* r = p + off;
-        off += k;
-        return r;
-    }
-};
-
-// A packed GEMM weight operand (device) + bias
-struct Packed {
+// A packed GEMM weight operand on the device: its shape (mx: wq / wsc are set) + bias
+struct Packed : PackShape {
     void* w = nullptr;          // [npad][kpad] elements of the compute type
     float* bias = nullptr;      // [npad]
-    int npad = 0, kpad = 0, N = 0, K = 0;
-    float alpha = 0.f;
-    int act = 0;
     uint8_t* wq = nullptr;      // dtype 2 (LSTM input projections, qualifying conv layers): e4m3 [npad8][kpad]
     uint8_t* wsc = nullptr;     //   and E8M0 scales [npad8][kpad / 32]
-    int npad8 = 0;              // rows of wq (a multiple of the MX GEMM's 256-column tile)
 };
 
 }  // namespace
 
 struct StreamState;
 
-struct aec_crn_handle {
-    aec_crn_config cfg{};
+struct aec_crn_handle : Net<Packed> {              // cfg, the derived sizes and the conv layers: crn_host.h
     int device = 0;
     std::string err;
-    int L = 6, D = 4, H = 0, S = 1, CELLS = 1, Q = 0, nrnn = 1;
-    size_t es = 4;                                 // element size
-    bool mx8 = false;                              // dtype 2: MX-fp8 LSTM input projections
     aec::DevTables* d_tab = nullptr;
-    std::vector<Packed> enc, dec;                  // dec: 2 per level (even, odd)
-    std::vector<Packed> decf;                      // per level: both parities in one GEMM (see pack_decoder_fused)
-    int dec_fuse_max = 128;                        // CRN_DEC_FUSE: fuse the parities of levels with <= this many
-                                                   // output channels (HBM-bound layers); 0 = never
     std::vector<Packed> lih, lhh;                  // per LSTM layer
     std::vector<Packed> lcat;                      // dtype 2, v2: [W_ih | W_hh] MX rows (lstm_step_mx8_kernel)
     bool have_params = false;
@@ -96,8 +57,6 @@ struct aec_crn_handle {
     void* xn = nullptr;
     uint8_t* aq = nullptr;                         // dtype 2: quantized rows + scales (layers without a shadow)
     uint8_t* as = nullptr;
-    bool mx8_shadow = true;                        // AEC_CRN_MX8_SHADOW=0 at create: every MX GEMM quantises its rows
-                                                   //   first (the A/B and bit-equality reference)
     std::vector<uint8_t*> cat8, cats;              // dtype 2: MX-fp8 shadows of cat[l] (null: none), see shadow_level
     uint8_t* xn8 = nullptr;                        //   and of xn
     uint8_t* xns = nullptr;
@@ -143,466 +102,50 @@ static aec_status crn_fail(aec_crn_handle* h, aec_status s, const std::string& m
     return s;
 }
 
-// --------------------------------------------------------------------------
-// config validation + parameter layout
-// --------------------------------------------------------------------------
-static std::string check_cfg(const aec_crn_config& c) {
-    if (c.version != 1 && c.version != 2) return "version must be 1 (dccrn.py) or 2 (dccrn2.py)";
-    if (c.n_layers < 1 || c.n_layers > 8) return "n_layers out of range";
-    if (256 >> c.n_layers != 4) return "the LSTM width needs 256 >> n_layers == 4 (dccrn.py:514)";
-    if (c.conv_channels[0] != 4) return "conv_channels[0] must be 4 (mic/far real/imag)";
-    for (int i = 1; i <= c.n_layers; ++i)
-        if (c.conv_channels[i] < 8 || ilog2(c.conv_channels[i]) < 0) return "conv_channels must be powers of two >= 8";
-    if (c.dtype < 0 || c.dtype > 2) return "dtype must be 0 (f32), 1 (bf16) or 2 (bf16 + MX-fp8 LSTM input)";
-    if (c.version == 2) {
-        if (c.hidden_dim != 4) return "hidden_dim must equal the encoder output width (4)";
-        if (c.rnn_layers < 1 || c.rnn_layers > 8) return "rnn_layers out of range";
-        if (c.masking_mode != 'E' && c.masking_mode != 'C' && c.masking_mode != 'R') return "masking_mode must be E, C or R";
-    }
-    if (c.nlms_taps < 0 || c.nlms_taps > 8) return "nlms_taps must be 0..8";
-    if (c.nlms_taps > 0 && !(c.nlms_mu >= 0.f && c.nlms_mu < 2.f && c.nlms_beta >= 0.f && c.nlms_beta < 1.f &&
-                             c.nlms_delta > 0.f))
-        return "NLMS needs mu in [0, 2), beta in [0, 1), delta > 0";
-    return "";
-}
-
-static size_t norm_count(const aec_crn_config& c, int ch) {
-    return (c.version == 2 && c.use_cbn) ? 10 * (size_t)(ch / 2) : 4 * (size_t)ch;
-}
-
-static size_t param_count(const aec_crn_config& c) {
-    if (!check_cfg(c).empty()) return 0;
-    const int* ch = c.conv_channels;
-    const int L = c.n_layers;
-    size_t n = 0;
-    for (int i = 0; i < L; ++i) {
-        const size_t co = ch[i + 1] / 2, ci = ch[i] / 2;
-        n += 2 * (co * ci * 5 + co) + norm_count(c, ch[i + 1]) + 1;
-    }
-    for (int cl = L; cl >= 1; --cl) {
-        const size_t ci = ch[cl], co = (cl != 1 ? ch[cl - 1] : 2) / 2;
-        n += 2 * (ci * co * 5 + co);
-        if (cl != 1)
-            n += norm_count(c, ch[cl - 1]) + 1;
-        else if (c.version == 1)
-            n += 4 * 2;
-    }
-    if (c.version == 1) {
-        const size_t H = (size_t)ch[L] * 4;
-        n += 2 * 4 * H * H + 2 * 4 * H;
-    } else {
-        const size_t H = (size_t)c.hidden_dim * ch[L] / 2;
-        n += (size_t)c.rnn_layers * 2 * (2 * 4 * H * H + 2 * 4 * H);
-    }
-    return n;
-}
-
-// --------------------------------------------------------------------------
-// folding: complex conv -> real [Co][Ci][5] (out x in, reference channel
-// order) + bias; then the eval norm as an affine map on the output channels
-// --------------------------------------------------------------------------
-struct RealConv {
-    int Co = 0, Ci = 0;
-    std::vector<double> w;   // [Co][Ci][5]
-    std::vector<double> b;   // [Co]
-    double& at(int o, int i, int k) { return w[((size_t)o * Ci + i) * 5 + k]; }
-};
-
-// ComplexConv2d (dccrn.py:140-153): weights [co'][ci'][5][1];
-// ComplexConvTranspose2d (dccrn.py:194-207): weights [ci'][co'][5][1].
-static RealConv complex_conv(Cursor& cur, int Ci, int Co, bool transposed) {
-    const int ci = Ci / 2, co = Co / 2;
-    const size_t nw = (size_t)ci * co * 5;
-    const float* wr = cur.take(nw);
-    const float* br = cur.take(co);
-    const float* wi = cur.take(nw);
-    const float* bi = cur.take(co);
-    RealConv r;
-    r.Co = Co;
-    r.Ci = Ci;
-    r.w.assign((size_t)Co * Ci * 5, 0.0);
-    r.b.assign(Co, 0.0);
-    if (!cur.ok) return r;
-    for (int o = 0; o < co; ++o)
-        for (int i = 0; i < ci; ++i)
-            for (int k = 0; k < 5; ++k) {
-                const size_t idx = transposed ? ((size_t)i * co + o) * 5 + k : ((size_t)o * ci + i) * 5 + k;
-                const double a = wr[idx], c = wi[idx];
-                r.at(o, i, k) = a;            // real <- real_conv(x_r)
-                r.at(o, ci + i, k) = -c;      //       - imag_conv(x_i)
-                r.at(co + o, i, k) = c;       // imag <- imag_conv(x_r)
-                r.at(co + o, ci + i, k) = a;  //       + real_conv(x_i)
-            }
-    for (int o = 0; o < co; ++o) {
-        r.b[o] = (double)br[o] - (double)bi[o];
-        r.b[co + o] = (double)bi[o] + (double)br[o];
-    }
-    return r;
-}
-
-// y = A z + c0 per output channel (pairs (o, co+o) for ComplexBatchNorm)
-static void fold_norm(Cursor& cur, RealConv& r, bool cbn) {
-    const int Co = r.Co;
-    const double eps = 1e-5;
-    std::vector<double> A((size_t)Co * Co, 0.0), c0(Co, 0.0);
-    if (cbn) {   // ComplexBatchNorm eval (dccrn.py:300-383)
-        const int c = Co / 2;
-        const float *Wrr = cur.take(c), *Wri = cur.take(c), *Wii = cur.take(c), *Br = cur.take(c), *Bi = cur.take(c);
-        const float *RMr = cur.take(c), *RMi = cur.take(c), *RVrr = cur.take(c), *RVri = cur.take(c),
-                    *RVii = cur.take(c);
-        if (!cur.ok) return;
-        for (int o = 0; o < c; ++o) {
-            const double Vrr = (double)RVrr[o] + eps, Vri = RVri[o], Vii = (double)RVii[o] + eps;
-            const double tau = Vrr + Vii;
-            const double s = std::sqrt(Vrr * Vii - Vri * Vri);
-            const double t = std::sqrt(tau + 2 * s);
-            const double rst = 1.0 / (s * t);
-            const double Urr = (s + Vii) * rst, Uii = (s + Vrr) * rst, Uri = -Vri * rst;
-            const double Zrr = Wrr[o] * Urr + Wri[o] * Uri;
-            const double Zri = Wrr[o] * Uri + Wri[o] * Uii;
-            const double Zir = Wri[o] * Urr + Wii[o] * Uri;
-            const double Zii = Wri[o] * Uri + Wii[o] * Uii;
-            A[(size_t)o * Co + o] = Zrr;
-            A[(size_t)o * Co + c + o] = Zri;
-            A[(size_t)(c + o) * Co + o] = Zir;
-            A[(size_t)(c + o) * Co + c + o] = Zii;
-            c0[o] = Br[o] - Zrr * RMr[o] - Zri * RMi[o];
-            c0[c + o] = Bi[o] - Zir * RMr[o] - Zii * RMi[o];
+// One packed operand to the device: the weights in the compute type + bias (npad == 0: an unfused
+// level, or MX rows only), the MX-fp8 rows (operands with mx); buffers are allocated on the first upload
+static aec_status upload(aec_crn_handle* h, Packed& pk, const HostPacked& hp) {
+    static_cast<PackShape&>(pk) = hp;
+    if (hp.npad > 0) {
+        const std::vector<uint8_t> hw = weight_bytes(hp, h->es);
+        const std::vector<float> hb = bias_floats(hp);
+        if (!pk.w) {
+            CRN_TRY(h, hipMalloc(&pk.w, hw.size()));
+            CRN_TRY(h, hipMalloc(&pk.bias, hb.size() * sizeof(float)));
         }
-    } else {     // BatchNorm2d eval
-        const float *w = cur.take(Co), *b = cur.take(Co), *rm = cur.take(Co), *rv = cur.take(Co);
-        if (!cur.ok) return;
-        for (int o = 0; o < Co; ++o) {
-            const double s = (double)w[o] / std::sqrt((double)rv[o] + eps);
-            A[(size_t)o * Co + o] = s;
-            c0[o] = (double)b[o] - s * rm[o];
+        CRN_TRY(h, hipMemcpy(pk.w, hw.data(), hw.size(), hipMemcpyHostToDevice));
+        CRN_TRY(h, hipMemcpy(pk.bias, hb.data(), hb.size() * 4, hipMemcpyHostToDevice));
+    }
+    if (hp.mx) {
+        if (!pk.wq) {
+            CRN_TRY(h, hipMalloc(&pk.wq, hp.q.size()));
+            CRN_TRY(h, hipMalloc(&pk.wsc, hp.sc.size()));
         }
+        CRN_TRY(h, hipMemcpy(pk.wq, hp.q.data(), hp.q.size(), hipMemcpyHostToDevice));
+        CRN_TRY(h, hipMemcpy(pk.wsc, hp.sc.data(), hp.sc.size(), hipMemcpyHostToDevice));
     }
-    RealConv f = r;
-    for (int o = 0; o < Co; ++o) {
-        for (size_t q = 0; q < (size_t)r.Ci * 5; ++q) {
-            double acc = 0;
-            for (int o2 = 0; o2 < Co; ++o2) {
-                const double a = A[(size_t)o * Co + o2];
-                if (a != 0.0) acc += a * r.w[(size_t)o2 * r.Ci * 5 + q];
-            }
-            f.w[(size_t)o * r.Ci * 5 + q] = acc;
-        }
-        double acc = c0[o];
-        for (int o2 = 0; o2 < Co; ++o2) acc += A[(size_t)o * Co + o2] * r.b[o2];
-        f.b[o] = acc;
-    }
-    r = f;
-}
-
-static aec_status upload_packed(aec_crn_handle* h, Packed& pk, const std::vector<double>& w,
-                                const std::vector<double>& b) {
-    const size_t n = (size_t)pk.npad * pk.kpad;
-    if (!pk.w) {
-        CRN_TRY(h, hipMalloc(&pk.w, n * h->es));
-        CRN_TRY(h, hipMalloc(&pk.bias, (size_t)pk.npad * sizeof(float)));
-    }
-    if (h->es == 4) {
-        std::vector<float> hw(n);
-        for (size_t i = 0; i < n; ++i) hw[i] = (float)w[i];
-        CRN_TRY(h, hipMemcpy(pk.w, hw.data(), n * 4, hipMemcpyHostToDevice));
-    } else {
-        std::vector<uint16_t> hw(n);
-        for (size_t i = 0; i < n; ++i) hw[i] = host_f2bf((float)w[i]);
-        CRN_TRY(h, hipMemcpy(pk.w, hw.data(), n * 2, hipMemcpyHostToDevice));
-    }
-    std::vector<float> hb(pk.npad, 0.f);
-    for (int i = 0; i < pk.N; ++i) hb[i] = (float)b[i];
-    CRN_TRY(h, hipMemcpy(pk.bias, hb.data(), hb.size() * 4, hipMemcpyHostToDevice));
     return AEC_OK;
-}
-
-// OCP e4m3 (e4m3fn) of x, round to nearest even, saturating at +-448
-static uint8_t host_e4m3(double x) {
-    const uint8_t sg = x < 0 ? 0x80 : 0;
-    const double a = std::fabs(x);
-    if (!(a < 448.0)) return sg | 0x7E;
-    if (a < std::ldexp(1.0, -6)) return sg | (uint8_t)std::nearbyint(a * 512.0);   // subnormal: m * 2^-9
-    int e2;
-    (void)std::frexp(a, &e2);
-    const int E = e2 - 1;                                                          // floor(log2 a), -6 .. 8
-    const int m = (int)std::nearbyint((a / std::ldexp(1.0, E) - 1.0) * 8.0);      // 0 .. 8 (8 carries)
-    const int code = std::min(((E + 7) << 3) + m, 0x7E);
-    return sg | (uint8_t)code;
-}
-
-// dtype 2: the packed weight rows [npad][kpad] as MX-fp8 (E8M0 scale per 32 k:
-// 2^(floor(log2 amax) - 8), the same rule as the device's activation quantizer)
-static aec_status upload_mx8(aec_crn_handle* h, Packed& pk, const std::vector<double>& w) {
-    pk.npad8 = (pk.N + 255) / 256 * 256;
-    const size_t n = (size_t)pk.npad8 * pk.kpad, kb = (size_t)pk.kpad / 32;
-    std::vector<uint8_t> q(n, 0), sc((size_t)pk.npad8 * kb, 0);
-    for (int r = 0; r < pk.N; ++r)
-        for (size_t b = 0; b < kb; ++b) {
-            const double* x = &w[(size_t)r * pk.kpad + b * 32];
-            double amax = 0;
-            for (int j = 0; j < 32; ++j) amax = std::max(amax, std::fabs((double)(float)x[j]));
-            int code = 0;
-            if (amax > 0) {
-                int e2;
-                (void)std::frexp((double)(float)amax, &e2);
-                code = std::max(0, std::min(254, (e2 - 1) + 127 - 8));
-            }
-            sc[(size_t)r * kb + b] = (uint8_t)code;
-            for (int j = 0; j < 32; ++j)
-                q[(size_t)r * pk.kpad + b * 32 + j] = host_e4m3(std::ldexp((double)(float)x[j], 127 - code));
-        }
-    if (!pk.wq) {
-        CRN_TRY(h, hipMalloc(&pk.wq, n));
-        CRN_TRY(h, hipMalloc(&pk.wsc, sc.size()));
-    }
-    CRN_TRY(h, hipMemcpy(pk.wq, q.data(), n, hipMemcpyHostToDevice));
-    CRN_TRY(h, hipMemcpy(pk.wsc, sc.data(), sc.size(), hipMemcpyHostToDevice));
-    return AEC_OK;
-}
-
-// dtype 2 also runs a conv layer on the MX-fp8 GEMM when its implicit rows
-// split into 32-k blocks inside one tap (2^kshift % 32 == 0), K is a whole
-// number of 128-k stages and the layer is wide enough (N >= 128) for the
-// 256-column MX tile: encoder layers 4-5 and decoder levels 5-6 of net_conf,
-// about 75 % of the conv FLOPs.
-static bool conv_mx8(const aec_crn_handle* h, const Packed& pk, int kshift_ch) {
-    return h->mx8 && pk.K % 128 == 0 && pk.kpad == pk.K && kshift_ch % 32 == 0 && pk.N >= 128;
-}
-
-static int kpad_for(int K, size_t es) {
-    const int per = (int)(crn::kStageBytes / es);
-    return (K + per - 1) / per * per;
-}
-
-// encoder layer: Bt[co][tap*Cin_buf + q] = W[co][q][tap]  (q < real input channels)
-static aec_status pack_encoder(aec_crn_handle* h, Packed& pk, const RealConv& r, int cin_buf, float alpha) {
-    pk.N = r.Co;
-    pk.K = 5 * cin_buf;
-    pk.npad = (r.Co + crn::gemm_bn(r.Co) - 1) / crn::gemm_bn(r.Co) * crn::gemm_bn(r.Co);
-    pk.kpad = kpad_for(pk.K, h->es);
-    pk.alpha = alpha;
-    pk.act = 1;
-    std::vector<double> w((size_t)pk.npad * pk.kpad, 0.0);
-    for (int o = 0; o < r.Co; ++o)
-        for (int k = 0; k < 5; ++k)
-            for (int q = 0; q < std::min(cin_buf, r.Ci); ++q)
-                w[(size_t)o * pk.kpad + k * cin_buf + q] = r.w[((size_t)o * r.Ci + q) * 5 + k];
-    aec_status s = upload_packed(h, pk, w, r.b);
-    if (s == AEC_OK && conv_mx8(h, pk, cin_buf)) s = upload_mx8(h, pk, w);
-    return s;
-}
-
-// decoder level: input buffer channels [dec_r, dec_i, enc_r, enc_i] (C each
-// half-pair) vs the reference complex_cat order [dec_r, enc_r, dec_i, enc_i]
-// (dccrn.py:386-395); parity 0: taps (4, 2, 0) at bins (m-1, m, m+1),
-// parity 1: taps (3, 1) at (m, m+1).
-static aec_status pack_decoder(aec_crn_handle* h, Packed& pk, const RealConv& r, int parity, int act, float alpha) {
-    const int Cin = r.Ci, C = Cin / 2;
-    const int ntap = parity == 0 ? 3 : 2;
-    pk.N = r.Co;
-    pk.K = ntap * Cin;
-    const int bn = crn::gemm_bn(r.Co);
-    pk.npad = (r.Co + bn - 1) / bn * bn;
-    pk.kpad = kpad_for(pk.K, h->es);
-    pk.alpha = alpha;
-    pk.act = act;
-    auto ref = [&](int q) {
-        if (q < C / 2) return q;
-        if (q < C) return C + (q - C / 2);
-        if (q < 3 * C / 2) return C / 2 + (q - C);
-        return q;
-    };
-    std::vector<double> w((size_t)pk.npad * pk.kpad, 0.0);
-    for (int o = 0; o < r.Co; ++o)
-        for (int j = 0; j < ntap; ++j) {
-            const int tap = parity == 0 ? 4 - 2 * j : 3 - 2 * j;
-            for (int q = 0; q < Cin; ++q)
-                w[(size_t)o * pk.kpad + j * Cin + q] = r.w[((size_t)o * Cin + ref(q)) * 5 + tap];
-        }
-    aec_status s = upload_packed(h, pk, w, r.b);
-    if (s == AEC_OK && act == 1 && conv_mx8(h, pk, Cin)) s = upload_mx8(h, pk, w);
-    return s;
-}
-
-// Both parities of a decoder level as ONE GEMM over the rows of parity 0
-// (bins m-1, m, m+1): columns [0, Co) parity 0 (taps 4, 2, 0), columns
-// [Co, 2 Co) parity 1 (zero at bin m-1, taps 3, 1 at m, m+1).  The
-// memory-bound levels read their input rows once instead of twice; the
-// epilogue routes the parity-1 columns to the odd output bins (RowEpi nsplit).
-static aec_status pack_decoder_fused(aec_crn_handle* h, Packed& pk, const RealConv& r, int act, float alpha) {
-    const int Cin = r.Ci, C = Cin / 2, Co = r.Co;
-    pk.N = 2 * Co;
-    pk.K = 3 * Cin;
-    const int bn = crn::gemm_bn(pk.N);
-    pk.npad = (pk.N + bn - 1) / bn * bn;
-    pk.kpad = kpad_for(pk.K, h->es);
-    pk.alpha = alpha;
-    pk.act = act;
-    auto ref = [&](int q) {
-        if (q < C / 2) return q;
-        if (q < C) return C + (q - C / 2);
-        if (q < 3 * C / 2) return C / 2 + (q - C);
-        return q;
-    };
-    std::vector<double> w((size_t)pk.npad * pk.kpad, 0.0), b(pk.N);
-    for (int o = 0; o < Co; ++o) {
-        b[o] = b[Co + o] = r.b[o];
-        for (int j = 0; j < 3; ++j)
-            for (int q = 0; q < Cin; ++q) {
-                w[(size_t)o * pk.kpad + j * Cin + q] = r.w[((size_t)o * Cin + ref(q)) * 5 + (4 - 2 * j)];
-                if (j > 0) w[(size_t)(Co + o) * pk.kpad + j * Cin + q] = r.w[((size_t)o * Cin + ref(q)) * 5 + (5 - 2 * j)];
-            }
-    }
-    aec_status s = upload_packed(h, pk, w, b);
-    // dtype 2: the wide levels on the MX GEMM (parity 1's zero tap is a whole number of 128-k
-    // stages, so each parity's sum is the unfused GEMM's, bit for bit)
-    if (s == AEC_OK && act == 1 && conv_mx8(h, pk, Cin)) s = upload_mx8(h, pk, w);
-    return s;
-}
-
-// LSTM cell(s): unit order u' = d*Q + c <-> reference u = c*D + d; W_hh gate
-// row p(q, u') = ((u'/16)*4 + q)*16 + u'%16 (i|f|g|o per 16 units), W_ih /
-// bias gate row u'*4 + q (so Gx holds a unit's 4 gates contiguously)
-static aec_status pack_lstm(aec_crn_handle* h, Cursor& cur, Packed& ih, Packed& hh, Packed& cat) {
-    const int H = h->H, D = h->D, Q = h->Q, C = h->CELLS;
-    const size_t G = (size_t)4 * H;
-    std::vector<double> wih((size_t)C * G * H), whh((size_t)C * G * H), bias((size_t)C * G);
-    // dtype 2, NavieComplexLSTM: [W_ih | W_hh] rows (K = 2H) in W_hh's row order for the fused
-    // per-hop layer step (lstm_step_mx8_kernel)
-    const bool want_cat = h->mx8 && C * h->S == 4 && H % 256 == 0;
-    std::vector<double> wcat(want_cat ? (size_t)C * G * 2 * H : 0);
-    auto perm = [&](int up) { return (up % Q) * D + up / Q; };
-    for (int cell = 0; cell < C; ++cell) {
-        const float* Wih = cur.take(G * H);
-        const float* Whh = cur.take(G * H);
-        const float* bih = cur.take(G);
-        const float* bhh = cur.take(G);
-        if (!cur.ok) return crn_fail(h, AEC_ERR_INVALID_ARG, "parameter blob too short");
-        for (int up = 0; up < H; ++up)
-            for (int q = 0; q < 4; ++q) {
-                // W_hh rows: fragment order (16 units of one gate per 16-column fragment);
-                // W_ih rows / bias: the 4 gates of a unit adjacent (Gx read as one vector)
-                const size_t p = (size_t)cell * G + ((size_t)(up / 16) * 4 + q) * 16 + up % 16;
-                const size_t pi = (size_t)cell * G + (size_t)up * 4 + q;
-                const size_t src = (size_t)q * H + perm(up);
-                for (int kp = 0; kp < H; ++kp) {
-                    wih[pi * H + kp] = Wih[src * H + perm(kp)];
-                    whh[p * H + kp] = Whh[src * H + perm(kp)];
-                }
-                if (want_cat)
-                    for (int kp = 0; kp < H; ++kp) {
-                        wcat[p * 2 * H + kp] = Wih[src * H + perm(kp)];
-                        wcat[p * 2 * H + H + kp] = Whh[src * H + perm(kp)];
-                    }
-                bias[pi] = (double)bih[src] + (double)bhh[src];
-            }
-    }
-    ih.N = hh.N = (int)(C * G);
-    ih.K = hh.K = H;
-    ih.npad = hh.npad = (int)(C * G);
-    ih.kpad = hh.kpad = H;
-    ih.act = 0;
-    aec_status s = upload_packed(h, ih, wih, bias);
-    if (s != AEC_OK) return s;
-    if (h->mx8) {
-        s = upload_mx8(h, ih, wih);
-        if (s != AEC_OK) return s;
-    }
-    s = upload_packed(h, hh, whh, bias);
-    if (s == AEC_OK && want_cat) {
-        cat.N = (int)(C * G);
-        cat.K = cat.kpad = 2 * H;
-        s = upload_mx8(h, cat, wcat);
-    }
-    return s;
 }
 
 static aec_status load_params(aec_crn_handle* h, const float* params, size_t n) {
-    const aec_crn_config& c = h->cfg;
-    if (n != param_count(c)) return crn_fail(h, AEC_ERR_INVALID_ARG, "parameter count mismatch");
-    Cursor cur{params, n};
-    const int* ch = c.conv_channels;
-    const int L = h->L;
-    const bool cbn = c.version == 2 && c.use_cbn;
-    for (int i = 0; i < L; ++i) {
-        RealConv r = complex_conv(cur, ch[i], ch[i + 1], false);
-        fold_norm(cur, r, cbn);
-        const float* a = cur.take(1);
-        if (!cur.ok) return crn_fail(h, AEC_ERR_INVALID_ARG, "parameter blob too short");
-        aec_status s = pack_encoder(h, h->enc[i], r, i == 0 ? 8 : ch[i], a[0]);
-        if (s != AEC_OK) return s;
+    HostNet net;
+    const std::string why = pack_network(*h, params, n, net);
+    if (!why.empty()) return crn_fail(h, AEC_ERR_INVALID_ARG, why);
+    aec_status s = AEC_OK;
+    for (int i = 0; i < h->L && s == AEC_OK; ++i) s = upload(h, h->enc[i], net.enc[i]);
+    for (int d = 0; d < h->L && s == AEC_OK; ++d) {
+        s = upload(h, h->dec[2 * d], net.dec[2 * d]);
+        if (s == AEC_OK) s = upload(h, h->dec[2 * d + 1], net.dec[2 * d + 1]);
+        if (s == AEC_OK) s = upload(h, h->decf[d], net.decf[d]);
     }
-    for (int d = 0; d < L; ++d) {
-        const int cl = L - d;
-        const int co = cl != 1 ? ch[cl - 1] : 2;
-        RealConv r = complex_conv(cur, 2 * ch[cl], co, true);
-        int act = 0;
-        float alpha = 0.f;
-        if (cl != 1) {
-            fold_norm(cur, r, cbn);
-            const float* a = cur.take(1);
-            if (!cur.ok) return crn_fail(h, AEC_ERR_INVALID_ARG, "parameter blob too short");
-            act = 1;
-            alpha = a[0];
-        } else if (c.version == 1) {   // BatchNorm2d(2) + Tanh (dccrn.py:494-506)
-            fold_norm(cur, r, false);
-            act = 2;
-        }
-        if (!cur.ok) return crn_fail(h, AEC_ERR_INVALID_ARG, "parameter blob too short");
-        for (int par = 0; par < 2; ++par) {
-            aec_status s = pack_decoder(h, h->dec[2 * d + par], r, par, act, alpha);
-            if (s != AEC_OK) return s;
-        }
-        // fused parities: bf16 / f32 stores of 16 B never straddle the parity
-        // split when Co % 8 == 0 (measured, C3 bf16 decoder: unfused 7.31 ms, fused up to
-        // Co = 64 6.58, 128 6.42, 256 6.61); with dtype fp8 the levels the MX GEMM takes
-        // (Co >= 128) are fused too (one launch per level instead of two in the per-hop step).
-        // The mask level (Co = 2, f32 [F][256][2]) is fused as well: the two parities' outputs of
-        // an input bin are the 4 adjacent floats of bins 2i, 2i + 1, so its rows need no split
-        if ((cl != 1 && co % 8 == 0 && (co <= h->dec_fuse_max || (h->mx8 && h->dec_fuse_max >= 0))) ||
-            (cl == 1 && h->dec_fuse_max >= 0)) {
-            aec_status s = pack_decoder_fused(h, h->decf[d], r, act, alpha);
-            if (s != AEC_OK) return s;
-        }
+    for (int l = 0; l < h->nrnn && s == AEC_OK; ++l) {
+        s = upload(h, h->lih[l], net.rnn[l].ih);
+        if (s == AEC_OK) s = upload(h, h->lhh[l], net.rnn[l].hh);
+        if (s == AEC_OK) s = upload(h, h->lcat[l], net.rnn[l].cat);
     }
-    for (int l = 0; l < h->nrnn; ++l) {
-        aec_status s = pack_lstm(h, cur, h->lih[l], h->lhh[l], h->lcat[l]);
-        if (s != AEC_OK) return s;
-    }
-    if (!cur.ok || cur.off != n) return crn_fail(h, AEC_ERR_INVALID_ARG, "parameter blob layout mismatch");
+    if (s != AEC_OK) return s;
     h->have_params = true;
     return AEC_OK;
-}
-
-// dtype 2: bytes per frame of the largest quantized row block (LSTM input
-// rows, or the implicit rows of an MX-fp8 conv layer)
-static size_t mx8_row_bytes(const aec_crn_handle* h) {
-    size_t m = (size_t)h->S * h->H;
-    for (int i = 0; i < h->L; ++i)
-        if (h->enc[i].wq) m = std::max(m, (size_t)(128 >> i) * h->enc[i].K);
-    for (int d = 0; d < h->L; ++d)
-        for (int par = 0; par < 2; ++par)
-            if (h->dec[2 * d + par].wq) m = std::max(m, (size_t)(256 >> (h->L - d)) * h->dec[2 * d + par].K);
-    return m;
-}
-
-// dtype 2: cat[l] gets an MX-fp8 shadow (written by every producer's epilogue,
-// read in place by the MX GEMMs: no separate quantisation pass) when an MX
-// layer consumes it and its rows qualify for the in-place gather (128 | 2^kshift):
-// encoder layer l, decoder level l, or the first LSTM layer (l == L)
-static bool shadow_level(const aec_crn_handle* h, int l) {
-    if (!h->mx8 || !h->mx8_shadow || l < 1 || l > h->L) return false;
-    // cat[L]'s dec half comes from the LSTM combine, which writes a shadow for NavieComplexLSTM (v2) only
-    if (l == h->L && h->CELLS * h->S != 4) return false;
-    const int* ch = h->cfg.conv_channels;
-    if (l < h->L && h->enc[l].wq && ch[l] % 128 == 0) return true;
-    const int d = h->L - l;
-    if ((h->dec[2 * d].wq || h->dec[2 * d + 1].wq) && (2 * ch[l]) % 128 == 0) return true;
-    return l == h->L && h->Q % 128 == 0 && (2 * ch[l]) % 128 == 0;
-}
-static bool shadow_xn(const aec_crn_handle* h) {
-    return h->mx8 && h->mx8_shadow && h->nrnn > 1 && h->Q % 128 == 0 && h->CELLS * h->S == 4;
 }
 
 static aec_status ensure_ws(aec_crn_handle* h, int64_t B, int64_t T) {
@@ -612,47 +155,36 @@ static aec_status ensure_ws(aec_crn_handle* h, int64_t B, int64_t T) {
     h->last_lens.clear();                          // d_len is reallocated below
     h->last_B = 0;                                 // and the NLMS rows with it
     const int64_t nB = std::max<int64_t>(B, h->ws_B), nT = std::max<int64_t>(T, h->ws_T);
-    const int64_t BT = nB * nT;
-    const size_t es = h->es;
-    auto alloc = [&](void** p, size_t bytes) {
-        hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16));
+    const WsBytes wb = ws_bytes(*h, nB, nT);
+    auto alloc = [&](auto** p, size_t bytes) {     // 0 bytes: the network has no such buffer
+        *p = nullptr;
+        if (bytes == 0) return hipSuccess;
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(bytes, 16));
         if (e == hipSuccess) h->allocs.push_back(*p);
         return e;
     };
-    const int* ch = h->cfg.conv_channels;
-    CRN_TRY(h, alloc(&h->x0, (size_t)BT * 256 * 8 * es));
+    CRN_TRY(h, alloc(&h->x0, wb.x0));
     h->cat.assign(h->L + 1, nullptr);
-    for (int l = 1; l <= h->L; ++l) CRN_TRY(h, alloc(&h->cat[l], (size_t)BT * (256 >> l) * 2 * ch[l] * es));
-    CRN_TRY(h, alloc(&h->gx, (size_t)BT * h->S * h->CELLS * 4 * h->H * es));
-    CRN_TRY(h, alloc(&h->y, (size_t)BT * h->CELLS * h->S * h->H * es));
-    if (h->nrnn > 1) CRN_TRY(h, alloc(&h->xn, (size_t)BT * h->S * h->H * es));
-    if (h->mx8) {
-        const size_t qb = (size_t)BT * mx8_row_bytes(h);
-        CRN_TRY(h, alloc(reinterpret_cast<void**>(&h->aq), qb));
-        CRN_TRY(h, alloc(reinterpret_cast<void**>(&h->as), qb / 32));
-    }
+    for (int l = 1; l <= h->L; ++l) CRN_TRY(h, alloc(&h->cat[l], wb.cat[l]));
+    CRN_TRY(h, alloc(&h->gx, wb.gx));
+    CRN_TRY(h, alloc(&h->y, wb.y));
+    CRN_TRY(h, alloc(&h->xn, wb.xn));
+    CRN_TRY(h, alloc(&h->aq, wb.aq));
+    CRN_TRY(h, alloc(&h->as, wb.as));
     h->cat8.assign(h->L + 1, nullptr);
     h->cats.assign(h->L + 1, nullptr);
-    for (int l = 1; l <= h->L; ++l)
-        if (shadow_level(h, l)) {
-            const size_t n8 = (size_t)BT * (256 >> l) * 2 * ch[l];
-            CRN_TRY(h, alloc(reinterpret_cast<void**>(&h->cat8[l]), n8));
-            CRN_TRY(h, alloc(reinterpret_cast<void**>(&h->cats[l]), n8 / 32));
-        }
-    h->xn8 = h->xns = nullptr;
-    if (shadow_xn(h)) {
-        const size_t n8 = (size_t)BT * h->S * h->H;
-        CRN_TRY(h, alloc(reinterpret_cast<void**>(&h->xn8), n8));
-        CRN_TRY(h, alloc(reinterpret_cast<void**>(&h->xns), n8 / 32));
+    for (int l = 1; l <= h->L; ++l) {
+        CRN_TRY(h, alloc(&h->cat8[l], wb.cat8[l]));
+        CRN_TRY(h, alloc(&h->cats[l], wb.cats[l]));
     }
-    CRN_TRY(h, alloc(reinterpret_cast<void**>(&h->cst), (size_t)nB * h->CELLS * h->S * h->H * sizeof(float)));
-    CRN_TRY(h, alloc(reinterpret_cast<void**>(&h->mask), (size_t)BT * 256 * 2 * sizeof(float)));
-    CRN_TRY(h, alloc(reinterpret_cast<void**>(&h->d_len), (size_t)nB * sizeof(int64_t)));
-    if (h->cfg.nlms_taps > 0) {
-        CRN_TRY(h, alloc(reinterpret_cast<void**>(&h->nrows), (size_t)BT * 512 * sizeof(float2)));
-        CRN_TRY(h, alloc(reinterpret_cast<void**>(&h->espec), (size_t)BT * 256 * sizeof(float2)));
-        CRN_TRY(h, alloc(reinterpret_cast<void**>(&h->ndummy), (size_t)nB * 256 * sizeof(float2)));
-    }
+    CRN_TRY(h, alloc(&h->xn8, wb.xn8));
+    CRN_TRY(h, alloc(&h->xns, wb.xns));
+    CRN_TRY(h, alloc(&h->cst, wb.cst));
+    CRN_TRY(h, alloc(&h->mask, wb.mask));
+    CRN_TRY(h, alloc(&h->d_len, wb.d_len));
+    CRN_TRY(h, alloc(&h->nrows, wb.nrows));
+    CRN_TRY(h, alloc(&h->espec, wb.espec));
+    CRN_TRY(h, alloc(&h->ndummy, wb.ndummy));
     h->ws_B = nB;
     h->ws_T = nT;
     return AEC_OK;
@@ -689,20 +221,10 @@ struct Bufs {
     int32_t skc_n = 0;
 };
 
-// K slices of an MX conv GEMM in the per-hop step (its grid alone covers a fraction of the
-// CUs): >= 3 stages of 128 k per slice.  Chosen per layer, never from the row count.
-static int conv_ksplit(int kpad) {
-    static const int mx = AEC_AB_KNOB("AEC_CRN_SPLITK", 4);
-    const int nst = kpad / 128;
-    int ks = 1;
-    while (ks * 2 <= mx && nst >= 6 * ks) ks *= 2;
-    return ks;
-}
-
-// an output with an MX-fp8 shadow (bf16 GEMM epilogues only)
+// an output with an MX-fp8 shadow
 template <typename T>
 static void set_shadow(crn::RowEpi& e, uint8_t* q8, uint8_t* qs) {
-    if (sizeof(T) == 2 && q8 && e.N % 128 == 0) {      // the 128-column tiles: 32-column groups in lane quads
+    if (q8 && shadow_cols(e.N, sizeof(T))) {
         e.q8 = q8;
         e.qs = qs;
     }
@@ -731,26 +253,6 @@ static aec_status mx8_gemm(aec_crn_handle* h, const crn::RowSrc& a, const uint8_
     CRN_TRY(h, crn::launch_mx8_quant(a, bf.aq, bf.as, st));
     CRN_TRY(h, crn::launch_gemm_mx8<T>(bf.aq, bf.as, wq, wsc, K, e, npad, st));
     return AEC_OK;
-}
-
-// split-K workspace the MX conv GEMMs of a B-row step need (conv_ksplit per layer)
-static void splitk_need(const aec_crn_handle* h, int64_t B, int64_t* bytes, int64_t* tiles) {
-    const int* ch = h->cfg.conv_channels;
-    *bytes = 0;
-    *tiles = 0;
-    auto need = [&](int64_t M, int N, int kpad) {
-        *bytes = std::max(*bytes, crn::mx8_splitk_bytes(M, N, conv_ksplit(kpad)));
-        *tiles = std::max(*tiles, crn::mx8_splitk_tiles(M, N));
-    };
-    for (int i = 0; i < h->L; ++i)
-        if (h->enc[i].wq) need(B * (128 >> i), ch[i + 1], h->enc[i].kpad);
-    for (int d = 0; d < h->L; ++d) {
-        if (h->decf[d].wq) need(B * (256 >> (h->L - d)), h->decf[d].N, h->decf[d].kpad);
-        for (int par = 0; par < 2; ++par) {
-            const Packed& pk = h->dec[2 * d + par];
-            if (pk.wq) need(B * (256 >> (h->L - d)), pk.N, pk.kpad);
-        }
-    }
 }
 
 // Batch forward: encoder levels 0-3 in one launch (crn_enc_batch_kernel) when the handle's
@@ -793,7 +295,7 @@ static int run_enc_batch_try(aec_crn_handle* h, const Bufs& bf, int64_t F, hipSt
         L.out = reinterpret_cast<bf16_t*>(bf.cat[i + 1]);
         L.ldo = 2 * ch[i + 1];
         L.choff = ch[i + 1];
-        if (bf.cat8 && bf.cat8[i + 1] && pk.N % 128 == 0) {   // set_shadow's rule
+        if (bf.cat8 && bf.cat8[i + 1] && shadow_cols(pk.N, sizeof(T))) {
             L.q8 = bf.cat8[i + 1];
             L.qs = bf.cats[i + 1];
         }
@@ -1430,7 +932,7 @@ static crn::StreamEncArgs stream_enc_args(aec_crn_handle* h, int B) {
         L.out = reinterpret_cast<bf16_t*>(ss.cat[i + 1]);
         L.ldo = 2 * ch[i + 1];
         L.choff = ch[i + 1];
-        if (shadow_level(h, i + 1)) {
+        if (shadow_level(*h, i + 1)) {
             L.q8 = ss.cat8[i + 1];
             L.qs = ss.cats[i + 1];
         }
@@ -1498,7 +1000,7 @@ static bool stream_dec_mx_ok(const aec_crn_handle* h) {
     const Packed& pk = h->decf[h->L - 4];
     const int ks = conv_ksplit(pk.kpad);
     return pk.wq && pk.wsc && pk.act == 1 && pk.N == 128 && pk.K == 768 && pk.kpad == 768 && ch[4] == 128 &&
-           ch[3] == 64 && shadow_level(h, 4) && h->ss->cat8.size() > 4 && h->ss->cat8[4] && h->ss->cats[4] && (ks == 1 || ks == 2);
+           ch[3] == 64 && shadow_level(*h, 4) && h->ss->cat8.size() > 4 && h->ss->cat8[4] && h->ss->cats[4] && (ks == 1 || ks == 2);
 }
 
 // encoder level 4 inside the fused front (MX-fp8 step, AEC_CRN_STREAM_FUSE bit 4, default on): its
@@ -1529,7 +1031,7 @@ static int stream_enc_levels(const aec_crn_handle* h) {
         const Packed& pk = h->enc[i];
         const int cin = i == 0 ? 8 : ch[i];
         if (pk.wq || pk.act != 1 || pk.N != (16 << i) || cin != (8 << i) || (pk.K + 31) / 32 != nc[i] ||
-            pk.kpad < 32 * nc[i] || shadow_level(h, i + 1))
+            pk.kpad < 32 * nc[i] || shadow_level(*h, i + 1))
             return 0;
         ++n;
     }
@@ -1679,31 +1181,12 @@ aec_status aec_crn_create(const aec_crn_config* cfg, const float* params, size_t
     if (!why.empty()) return AEC_ERR_UNSUPPORTED;
     aec_crn_handle* h = new (std::nothrow) aec_crn_handle();
     if (!h) return AEC_ERR_OOM;
-    h->cfg = *cfg;
     h->device = device;
-    h->L = cfg->n_layers;
-    h->D = 256 >> h->L;
-    h->es = cfg->dtype == 0 ? 4 : 2;
-    h->mx8 = cfg->dtype == 2;
-    if (cfg->version == 1) {
-        h->H = cfg->conv_channels[h->L] * 4;
-        h->S = h->CELLS = 1;
-        h->nrnn = 1;
-    } else {
-        h->H = cfg->hidden_dim * cfg->conv_channels[h->L] / 2;
-        h->S = h->CELLS = 2;
-        h->nrnn = cfg->rnn_layers;
-    }
-    h->Q = h->H / h->D;
-    if (h->mx8 && (h->H % 128 || h->Q % 32)) {     // MX blocks of 32 k inside one tap, 128-k stages
-        delete h;
-        return AEC_ERR_UNSUPPORTED;
-    }
     auto bail = [&](aec_status s) {
         aec_crn_destroy(h);
         return s;
     };
-    if (h->H % 32 || ilog2(h->Q) < 0) return bail(AEC_ERR_UNSUPPORTED);
+    if (!set_dims(*h, *cfg).empty()) return bail(AEC_ERR_UNSUPPORTED);
     aec::DeviceGuard dg(device);
     if (dg.err != hipSuccess) return bail(AEC_ERR_HIP);
     if (hipMalloc(&h->d_tab, sizeof(aec::DevTables)) != hipSuccess) return bail(AEC_ERR_OOM);
@@ -1850,42 +1333,36 @@ aec_status aec_crn_stream_open(aec_crn_handle* h, int32_t B) {
     StreamState& ss = *h->ss;
     ss.B = B;
     const size_t es = h->es;
-    const int* ch = h->cfg.conv_channels;
     const int C = h->CELLS, S = h->S, H = h->H;
-    auto alloc = [&](void** p, size_t bytes) {
-        hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16));
+    auto alloc = [&](auto** p, size_t bytes) {     // 0 bytes: the network has no such buffer
+        if (bytes == 0) return hipSuccess;
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(bytes, 16));
         if (e == hipSuccess) {
             ss.allocs.push_back(*p);
             e = hipMemset(*p, 0, std::max<size_t>(bytes, 16));
         }
         return e;
     };
-    CRN_TRY(h, alloc(&ss.x0, (size_t)B * 256 * 8 * es));
+    const WsBytes wb = ws_bytes(*h, B, 1);         // the feature buffers of one frame per stream
+    CRN_TRY(h, alloc(&ss.x0, wb.x0));
     ss.cat.assign(h->L + 1, nullptr);
-    for (int l = 1; l <= h->L; ++l) CRN_TRY(h, alloc(&ss.cat[l], (size_t)B * (256 >> l) * 2 * ch[l] * es));
-    CRN_TRY(h, alloc(&ss.gx, (size_t)B * S * C * 4 * H * es));
-    if (h->nrnn > 1) CRN_TRY(h, alloc(&ss.xn, (size_t)B * S * H * es));
-    if (h->mx8) {
-        const size_t qb = (size_t)B * mx8_row_bytes(h);
-        CRN_TRY(h, alloc(reinterpret_cast<void**>(&ss.aq), qb));
-        CRN_TRY(h, alloc(reinterpret_cast<void**>(&ss.as), qb / 32));
-    }
+    for (int l = 1; l <= h->L; ++l) CRN_TRY(h, alloc(&ss.cat[l], wb.cat[l]));
+    CRN_TRY(h, alloc(&ss.gx, wb.gx));
+    CRN_TRY(h, alloc(&ss.xn, wb.xn));
+    CRN_TRY(h, alloc(&ss.aq, wb.aq));
+    CRN_TRY(h, alloc(&ss.as, wb.as));
     ss.cat8.assign(h->L + 1, nullptr);
     ss.cats.assign(h->L + 1, nullptr);
-    for (int l = 1; l <= h->L; ++l)
-        if (shadow_level(h, l)) {
-            const size_t n8 = (size_t)B * (256 >> l) * 2 * ch[l];
-            CRN_TRY(h, alloc(reinterpret_cast<void**>(&ss.cat8[l]), n8));
-            CRN_TRY(h, alloc(reinterpret_cast<void**>(&ss.cats[l]), n8 / 32));
-        }
-    if (shadow_xn(h)) {
-        CRN_TRY(h, alloc(reinterpret_cast<void**>(&ss.xn8), (size_t)B * S * H));
-        CRN_TRY(h, alloc(reinterpret_cast<void**>(&ss.xns), (size_t)B * S * H / 32));
+    for (int l = 1; l <= h->L; ++l) {
+        CRN_TRY(h, alloc(&ss.cat8[l], wb.cat8[l]));
+        CRN_TRY(h, alloc(&ss.cats[l], wb.cats[l]));
     }
-    CRN_TRY(h, alloc(reinterpret_cast<void**>(&ss.mask), (size_t)B * 256 * 2 * sizeof(float)));
+    CRN_TRY(h, alloc(&ss.xn8, wb.xn8));
+    CRN_TRY(h, alloc(&ss.xns, wb.xns));
+    CRN_TRY(h, alloc(&ss.mask, wb.mask));
     if (h->mx8) {
         int64_t skb = 0, skt = 0;
-        splitk_need(h, B, &skb, &skt);
+        splitk_need(*h, B, &skb, &skt);
         if (skb > 0 && skt <= INT32_MAX) {
             CRN_TRY(h, alloc(reinterpret_cast<void**>(&ss.skp), (size_t)skb));
             CRN_TRY(h, alloc(reinterpret_cast<void**>(&ss.skc), (size_t)skt * sizeof(int)));   // zeroed
@@ -1899,7 +1376,7 @@ aec_status aec_crn_stream_open(aec_crn_handle* h, int32_t B) {
     ss.mx_step = step_mx != 0 && h->mx8 && C * S == 4 && h->nrnn > 0 && h->lcat[0].wq != nullptr;
     if (ss.mx_step && h->nrnn > 2) {
         CRN_TRY(h, alloc(&ss.xnb, (size_t)B * S * H * es));
-        if (shadow_xn(h)) {
+        if (shadow_xn(*h)) {
             CRN_TRY(h, alloc(reinterpret_cast<void**>(&ss.xn8b), (size_t)B * S * H));
             CRN_TRY(h, alloc(reinterpret_cast<void**>(&ss.xnsb), (size_t)B * S * H / 32));
         }

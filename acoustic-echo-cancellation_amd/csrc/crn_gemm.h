@@ -22,6 +22,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "crn_host.h"
+
 namespace crn {
 
 typedef uint16_t bf16_t;
@@ -107,7 +109,6 @@ __device__ __forceinline__ float2 apply_mask(float2 x, float2 mk) {
     }
 }
 
-constexpr int kStageBytes = 128;   // K bytes staged per main-loop step (two 64-B k-chunks)
 constexpr int kRowStride = 144;    // LDS bytes per staged row: 16 rows at one column hit 16 distinct 16-B bank slots
 
 // Implicit-GEMM row source shared by the conv, LSTM-input and dense loaders:

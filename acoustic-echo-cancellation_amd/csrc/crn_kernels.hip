@@ -1405,10 +1405,6 @@ static hipError_t launch_mx8_cfg(const uint8_t* aq, const uint8_t* as, const uin
     return hipGetLastError();
 }
 
-// split-K runs the 64 x 64 tile (launch_mx8_any)
-int64_t mx8_splitk_tiles(int64_t M, int N) { return (M + 63) / 64 * ((N + 63) / 64); }
-int64_t mx8_splitk_bytes(int64_t M, int N, int ksplit) { return mx8_splitk_tiles(M, N) * ksplit * 64 * 64 * 4; }
-
 // 256 x 256 tiles (8 waves, 128 x 64 per wave) for the batch GEMMs; 64 x 64
 // tiles (2 waves) when the 256-tile grid would not cover the CUs (the
 // per-hop streaming step: M = streams x bins)

@@ -97,8 +97,6 @@ struct RowEpi {
     int* skc = nullptr;
     int64_t sk_bytes = 0;
 };
-int64_t mx8_splitk_tiles(int64_t M, int N);
-int64_t mx8_splitk_bytes(int64_t M, int N, int ksplit);
 
 // One LSTM frame step for CELLS weight sets x S input sequences (v1: 1x1,
 // v2 NavieComplexLSTM: 2x2), gate columns packed per 16 units (i|f|g|o).
@@ -363,8 +361,5 @@ bool persist_supported(int H, int cells, int seqs, int num_cus);
 // the team's rows in two halves whose phases alternate, so each half's cell
 // update and hand-off run under the other half's MFMAs
 hipError_t launch_lstm_persist(const PersistArgs& a, hipStream_t st);
-
-// tile width the host must pad the weight rows (N) to for a GEMM of N columns
-inline int gemm_bn(int N) { return N <= 16 ? 16 : N <= 32 ? 32 : N <= 64 ? 64 : 128; }
 
 }  // namespace crn

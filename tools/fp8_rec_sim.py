@@ -2,7 +2,7 @@
 """CPU estimate of the output error an MX-fp8 LSTM recurrence adds (C5 per-hop
 step): the torch DCCRN port (oracle/torch_crn_port.py,
 net_conf, v2) with W_hh and h_{t-1} rounded to OCP e4m3 with one E8M0 scale
-per 32 k (the device quantiser's rule, crn_api.hip upload_mx8) against the f32
+per 32 k (the device quantiser's rule, crn_host.h quantize_mx8) against the f32
 port.  Also rounds the LSTM input projections' operands the same way (the
 fp8 path of round 2) so the two error sources can be compared.
 
