@@ -26,7 +26,7 @@ _STATUS = {0: 'AEC_OK', 1: 'AEC_ERR_INVALID_ARG', 2: 'AEC_ERR_OOM', 3: 'AEC_ERR_
 EXPORTS = ('aec_weights_count', 'aec_create', 'aec_set_weights', 'aec_set_erb', 'aec_set_canceller', 'aec_process',
            'aec_process_siglens',
            'aec_prepare', 'aec_prepare_siglens', 'aec_process_prepared',
-           'aec_stream_open', 'aec_stream_reset', 'aec_stream_step',
+           'aec_stream_open', 'aec_stream_reset', 'aec_stream_step', 'aec_stream_push',
            'aec_set_debug', 'aec_debug_copy', 'aec_profile_enable', 'aec_profile_read',
            'aec_erb_tables_check', 'aec_num_frames', 'aec_out_len', 'aec_last_error', 'aec_destroy',
            'aec_set_weights_device', 'aec_train_forward', 'aec_train_backward', 'aec_train_generation',
@@ -104,6 +104,8 @@ def load():
     lib.aec_stream_reset.restype = ctypes.c_int
     lib.aec_stream_step.argtypes = [P, P, P, ctypes.c_int64, P, ctypes.c_int64, P]
     lib.aec_stream_step.restype = ctypes.c_int
+    lib.aec_stream_push.argtypes = [P, P, P, ctypes.c_int64, P, ctypes.c_int64, P, ctypes.c_int32, P]
+    lib.aec_stream_push.restype = ctypes.c_int
     lib.aec_set_debug.argtypes = [P, ctypes.c_int32]
     lib.aec_set_debug.restype = ctypes.c_int
     lib.aec_debug_copy.argtypes = [P, ctypes.c_int32, P, ctypes.c_size_t, P]
@@ -285,6 +287,11 @@ class Handle:
     def stream_step(self, mic_ptr, ref_ptr, ld_in, out_ptr, ld_out, stream):
         check(self.lib.aec_stream_step(self.h, mic_ptr, ref_ptr, int(ld_in), out_ptr, int(ld_out), stream), self.h,
               'aec_stream_step')
+
+    def stream_push(self, mic_ptr, ref_ptr, ld_in, out_ptr, ld_out, hops_ptr, max_hops, stream):
+        """hops_ptr: device [B] int32 hop counts, or None (every stream advances max_hops)"""
+        check(self.lib.aec_stream_push(self.h, mic_ptr, ref_ptr, int(ld_in), out_ptr, int(ld_out), hops_ptr,
+                                       int(max_hops), stream), self.h, 'aec_stream_push')
 
     def debug_copy(self, what, dst_ptr, n, stream):
         check(self.lib.aec_debug_copy(self.h, int(what), dst_ptr, int(n), stream), self.h, 'aec_debug_copy')

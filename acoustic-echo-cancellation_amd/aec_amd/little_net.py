@@ -376,6 +376,47 @@ class Little_net(nn.Module):
                           torch.cuda.current_stream(device).cuda_stream)
         return out
 
+    def stream_push(self, mic, ref, hops=None):
+        """Advance each stream by a packet of hops in one launch (aec_stream_push).
+
+        mic, ref [B, W] float32 on the streams' device, W >= 256, K = W // 256:
+        row b holds stream b's next hops back to back from column 0, already
+        normalised as for ``stream_step``.  ``hops``: None (every stream
+        advances K hops), an int32 tensor [B] on that device (each count is
+        clamped to [0, K] by the kernel; nothing synchronises), or a Python
+        sequence of B ints, which is uploaded — that copy synchronises with
+        the host.  Returns [B, 256 K] float32: row b's first 256 hops[b] samples
+        are what hops[b] ``stream_step`` calls would have returned; with counts
+        the tensor is allocated as zeros, so the rest of a row is zero (without
+        counts every row is written in full).  A stream with 0 hops keeps its
+        state."""
+        h, device, B = self._stream_state()
+        for t in (mic, ref):
+            if t.device != device or t.dim() != 2 or t.shape[0] != B or t.shape[1] < HOP:
+                raise ValueError(f'packets must be [{B}, >= 256] on {device}')
+        if mic.shape[1] != ref.shape[1]:
+            raise ValueError(f'mic and ref packets differ in width: {mic.shape[1]} / {ref.shape[1]}')
+        K = mic.shape[1] // HOP
+        if hops is not None:
+            if not torch.is_tensor(hops):
+                hops = torch.tensor([int(v) for v in hops], dtype=torch.int32).to(device)
+            if hops.device != device or hops.dtype != torch.int32 or hops.dim() != 1 or hops.shape[0] != B:
+                raise ValueError(f'hops must be an int32 tensor [{B}] on {device}')
+            hops = hops.contiguous()
+        mic = mic.float()
+        ref = ref.float()
+        if mic.stride(1) != 1 or ref.stride(1) != 1 or mic.stride(0) != ref.stride(0) or mic.stride(0) < HOP * K:
+            mic, ref = mic.contiguous(), ref.contiguous()
+        self._handle(device)            # weights may have changed
+        # zeros define what the kernel leaves unwritten; without counts every row is written in full
+        alloc = torch.empty if hops is None else torch.zeros
+        out = alloc(B, HOP * K, device=device, dtype=torch.float32)
+        with torch.cuda.device(device):
+            h.stream_push(mic.data_ptr(), ref.data_ptr(), mic.stride(0), out.data_ptr(), HOP * K,
+                          hops.data_ptr() if hops is not None else None, K,
+                          torch.cuda.current_stream(device).cuda_stream)
+        return out
+
     def debug_intermediate(self, what, B, T, device=None):
         """Copy an intermediate of the last forward: 'mic_erb', 'ref_erb',
         'near_erb', 'gru_out', 'mask', 'est_erb' -> [B, T, 32]."""

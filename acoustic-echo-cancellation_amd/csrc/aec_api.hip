@@ -820,6 +820,32 @@ aec_status aec_stream_step(aec_handle* h, const float* mic, const float* ref, in
     return AEC_OK;
 }
 
+aec_status aec_stream_push(aec_handle* h, const float* mic, const float* ref, int64_t ld_in, float* out,
+                           int64_t ld_out, const int32_t* hops, int32_t max_hops, void* stream) {
+    if (!h) return AEC_ERR_INVALID_ARG;
+    if (!h->d_state) return fail(h, AEC_ERR_INVALID_ARG, "aec_stream_open first");
+    if (!h->have_w || !h->have_erb) return fail(h, AEC_ERR_INVALID_ARG, "weights / erb not set");
+    if (!mic || !ref || !out) return fail(h, AEC_ERR_INVALID_ARG, "null mic / ref / out");
+    const Check c = check_stream_push(max_hops, ld_in, ld_out);
+    if (c.status != AEC_OK) return fail(h, c.status, c.why);
+    AEC_ON_DEVICE(h);
+    StreamPushArgs a{};
+    a.s.mic = mic; a.s.ref = ref; a.s.ld_in = ld_in; a.s.out = out; a.s.ld_out = ld_out;
+    a.s.state = h->d_state; a.s.state_stride = h->stream_stride;
+    a.s.w = h->d_w; a.s.tables = reinterpret_cast<const float*>(h->d_tab);
+    a.s.sched = h->d_sched; a.s.sched_len = h->sched_len; a.s.bintab = h->d_bintab;
+    a.s.mu = h->cfg.nlms_mu; a.s.beta = h->cfg.nlms_beta; a.s.delta = h->cfg.nlms_delta;
+    if (h->kalman) { a.s.kalman = 1; a.s.mu = h->kal_a; a.s.p0 = h->kal_p0; }
+    a.hops = hops; a.max_hops = max_hops;
+    // one hop for every stream is the step: the same result from the kernel without the hop loop
+    if (!hops && max_hops == 1) {
+        HIP_TRY(h, launch_stream_step(a.s, h->stream_B, h->cfg.nlms_taps, reinterpret_cast<hipStream_t>(stream)));
+        return AEC_OK;
+    }
+    HIP_TRY(h, launch_stream_push(a, h->stream_B, h->cfg.nlms_taps, reinterpret_cast<hipStream_t>(stream)));
+    return AEC_OK;
+}
+
 // ---------------------------------------------------------------------------
 // Training step (scripts/train1.py:191-218; kernels in aec_train.hip)
 // ---------------------------------------------------------------------------

@@ -260,6 +260,17 @@ inline Check check_lengths3(const int64_t* lengths3, int32_t B, int nsig, int64_
     return {};
 }
 
+// aec_stream_push's packet shape: every row must hold max_hops hops of 256 samples (the per-stream
+// counts are device data the kernel clamps to [0, max_hops]); the product is formed in 64 bits, so
+// max_hops has no limit of its own
+inline Check check_stream_push(int32_t max_hops, int64_t ld_in, int64_t ld_out) {
+    if (max_hops < 1) return {AEC_ERR_INVALID_ARG, "max_hops must be >= 1"};
+    const int64_t need = (int64_t)256 * max_hops;
+    if (ld_in < need) return {AEC_ERR_INVALID_ARG, "ld_in must be >= 256 max_hops"};
+    if (ld_out < need) return {AEC_ERR_INVALID_ARG, "ld_out must be >= 256 max_hops"};
+    return {};
+}
+
 // dst[B][4] = (mic, ref, near, 0) lengths as the kernels read them (normaliser
 // + zero padding); a signal that is not given takes mic's length
 inline void fill_slen(int32_t* dst, const int64_t* lengths3, int32_t B, int nsig) {

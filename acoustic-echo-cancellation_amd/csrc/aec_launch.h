@@ -129,6 +129,15 @@ struct StreamStepArgs {
     float p0;                //    p0 the initial tap covariance
 };
 
+// A packet of hops per stream in one launch (aec_stream.hip, aec_stream_push): s.mic / s.ref rows
+// hold stream b's next hops back to back, s.out receives as many output hops; the state layout at
+// the call's boundaries is the step's (above), so the two calls mix on one state.
+struct StreamPushArgs {
+    StreamStepArgs s;
+    const int32_t* hops;     // device [B] hop counts, clamped to [0, max_hops] by the kernel; null: max_hops each
+    int32_t max_hops;
+};
+
 // dynamic LDS bytes (must match the carve in the kernels)
 inline size_t analysis_smem_bytes(int sched_len) {
     return (size_t)sched_len * 16 * 16 + 32 * 8 + (258 * 2 + 256 * 2 + 512 + (size_t)kFPB * kGroupFloats) * 4;
@@ -167,6 +176,7 @@ hipError_t launch_mic_erb(const float2* spec, float* feats, const int64_t* lens,
 hipError_t launch_gru(const GruArgs& a, int B, hipStream_t st);
 hipError_t launch_synthesis(const SynthArgs& a, hipStream_t st);
 hipError_t launch_stream_step(const StreamStepArgs& a, int B, int taps, hipStream_t st);
+hipError_t launch_stream_push(const StreamPushArgs& a, int B, int taps, hipStream_t st);
 hipError_t launch_stream_cov_fill(float* state, int64_t stride, int first, int count, int taps, float p0,
                                   hipStream_t st);
 // K3+K4 fused (aec_gru_synth.hip): GRU + head + synthesis of the NLMS error spectrum, one stream per

@@ -181,6 +181,32 @@ aec_status aec_stream_reset(aec_handle* h, int32_t b, void* stream);
 aec_status aec_stream_step(aec_handle* h, const float* mic, const float* ref, int64_t ld_in,
                            float* out, int64_t ld_out, void* stream);
 
+/* A packet of hops per stream in ONE launch: stream b advances hops[b] hops
+ * (network audio arrives in packets of 20 .. 64 ms with jitter, so on one tick
+ * some streams have several hops queued and some none).  State, tables and
+ * weights stay on chip between the hops of a packet; the result is, bit for
+ * bit, what the same hops give through aec_stream_step one by one.
+ *   mic, ref: device [B, ld_in] float32; row b holds stream b's next hops[b]
+ *             hops back to back (256 hops[b] samples from column 0), normalised
+ *             as for aec_stream_step
+ *   out:      device [B, ld_out]; row b receives 256 hops[b] samples, column
+ *             block j being what the j-th of hops[b] consecutive
+ *             aec_stream_step calls would have written (the first block after
+ *             open / reset is the warm-up hop); the rest of the row is not written
+ *   hops:     DEVICE pointer to [B] int32 (a serving loop need not synchronise
+ *             to pass it), or NULL: every stream advances max_hops.  Each count
+ *             is clamped to [0, max_hops] by the kernel; a stream with 0 hops is
+ *             left exactly as it was (no byte of its state or out row changes)
+ *   max_hops: >= 1, with ld_in, ld_out >= 256 max_hops; no other limit
+ *             (max_hops == 1 with hops == NULL launches aec_stream_step's kernel)
+ * aec_stream_step, aec_stream_push and aec_stream_reset mix freely on one
+ * handle (one state layout at call boundaries), for nlms_taps 0..8 and both
+ * cancellers.  AEC_ERR_INVALID_ARG (text in aec_last_error): no open stream
+ * state, weights / ERB not set, null mic / ref / out, max_hops < 1, ld_in or
+ * ld_out below 256 max_hops. */
+aec_status aec_stream_push(aec_handle* h, const float* mic, const float* ref, int64_t ld_in,
+                           float* out, int64_t ld_out, const int32_t* hops, int32_t max_hops, void* stream);
+
 /* Debug / parity: copy an intermediate of the LAST aec_process call into the
  * device buffer dst ([B, T_max, 32] float32, frames beyond a stream's T left
  * unspecified).  Requires aec_set_debug(h, 1) before that call.

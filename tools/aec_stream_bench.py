@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
-"""Streaming Little_net latency (include/aec_hip.h aec_stream_step): B
-concurrent streams, one 256-sample hop per call = one fused kernel launch
-(STFT -> [FD-NLMS] -> ERB -> GRU step -> head -> iSTFT / OLA).  Prints the
-per-hop wall time (host loop, device-synchronised at the end), the HIP-event
-kernel time per hop and the real-time factor."""
+"""Streaming Little_net latency (include/aec_hip.h aec_stream_step /
+aec_stream_push): B concurrent streams, one fused kernel launch (STFT ->
+[FD-NLMS / Kalman] -> ERB -> GRU step -> head -> iSTFT / OLA) per 256-sample
+hop (--packet 1: stream_step) or per packet of K hops (--packet K:
+stream_push, every stream advancing K hops).  Prints the per-hop wall time
+(host loop over the same number of hops, device-synchronised at the end), the
+HIP-event time per hop (median over 50 timed calls, divided by K) and the
+real-time factor."""
 import argparse
 import json
 import os
@@ -22,31 +25,37 @@ ap = argparse.ArgumentParser()
 ap.add_argument('--B', type=int, default=256)
 ap.add_argument('--taps', type=int, default=4, help='NLMS taps (0 = post-filter only)')
 ap.add_argument('--hops', type=int, default=500)
+ap.add_argument('--packet', type=int, default=1, help='hops per call: 1 = stream_step, K > 1 = stream_push')
+ap.add_argument('--kalman', action='store_true', help='the Kalman canceller instead of the FD-NLMS')
+ap.add_argument('--push', action='store_true', help='with --packet 1: time stream_push instead of stream_step')
 a = ap.parse_args()
+if a.packet < 1 or a.hops % a.packet:
+    ap.error('--packet must be >= 1 and divide --hops')
 torch.manual_seed(0)
-nlms = dict(aec_amd.nlms_conf, taps=a.taps) if a.taps else None
+nlms = dict(aec_amd.kalman_conf if a.kalman else aec_amd.nlms_conf, taps=a.taps) if a.taps else None
 net = aec_amd.Little_net(aec_amd.speech_conf, 32, nlms=nlms).eval().cuda()
 erb = torch.tensor(EquivalentRectangularBandwidth(257, 16000, 32, 0, 8000).filters, dtype=torch.float32).cuda()
 net.stream_open(a.B, erb)
-mic = 0.1 * torch.randn(a.B, 256, device='cuda')
-far = 0.1 * torch.randn(a.B, 256, device='cuda')
+mic = 0.1 * torch.randn(a.B, 256 * a.packet, device='cuda')
+far = 0.1 * torch.randn(a.B, 256 * a.packet, device='cuda')
+call = net.stream_push if a.packet > 1 or a.push else net.stream_step
 with torch.no_grad():
     for _ in range(20):
-        net.stream_step(mic, far)
+        call(mic, far)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(a.hops):
-        net.stream_step(mic, far)
+    for _ in range(a.hops // a.packet):
+        call(mic, far)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / a.hops
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     ks = []
     for _ in range(50):
         e0.record()
-        net.stream_step(mic, far)
+        call(mic, far)
         e1.record()
         e1.synchronize()
-        ks.append(e0.elapsed_time(e1))
+        ks.append(e0.elapsed_time(e1) / a.packet)
 print(json.dumps(dict(B=a.B, nlms_taps=a.taps, ms_per_hop=round(dt * 1e3, 4),
                       event_ms_per_hop_median=round(float(np.median(ks)), 4), hop_ms=16.0,
-                      rtf=round(dt / 0.016, 5), frames_per_s=round(a.B / dt, 1))))
+                      rtf=round(dt / 0.016, 5), frames_per_s=round(a.B / dt, 1), packet=a.packet)))
