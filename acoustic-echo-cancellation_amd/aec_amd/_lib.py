@@ -27,6 +27,7 @@ EXPORTS = ('aec_weights_count', 'aec_create', 'aec_set_weights', 'aec_set_erb', 
            'aec_process_siglens',
            'aec_prepare', 'aec_prepare_siglens', 'aec_process_prepared',
            'aec_stream_open', 'aec_stream_reset', 'aec_stream_step', 'aec_stream_push',
+           'aec_delay_estimate', 'aec_delay_apply',
            'aec_set_debug', 'aec_debug_copy', 'aec_profile_enable', 'aec_profile_read',
            'aec_erb_tables_check', 'aec_num_frames', 'aec_out_len', 'aec_last_error', 'aec_destroy',
            'aec_set_weights_device', 'aec_train_forward', 'aec_train_backward', 'aec_train_generation',
@@ -106,6 +107,11 @@ def load():
     lib.aec_stream_step.restype = ctypes.c_int
     lib.aec_stream_push.argtypes = [P, P, P, ctypes.c_int64, P, ctypes.c_int64, P, ctypes.c_int32, P]
     lib.aec_stream_push.restype = ctypes.c_int
+    if LIB_PATH == _DEFAULT_LIB or hasattr(lib, 'aec_delay_estimate'):   # absent from an older A/B build
+        lib.aec_delay_estimate.argtypes = [P, P, P, P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, P, P, P]
+        lib.aec_delay_estimate.restype = ctypes.c_int
+        lib.aec_delay_apply.argtypes = [P, P, P, ctypes.c_int32, ctypes.c_int64, P, P, ctypes.c_int64, P]
+        lib.aec_delay_apply.restype = ctypes.c_int
     lib.aec_set_debug.argtypes = [P, ctypes.c_int32]
     lib.aec_set_debug.restype = ctypes.c_int
     lib.aec_debug_copy.argtypes = [P, ctypes.c_int32, P, ctypes.c_size_t, P]
@@ -292,6 +298,20 @@ class Handle:
         """hops_ptr: device [B] int32 hop counts, or None (every stream advances max_hops)"""
         check(self.lib.aec_stream_push(self.h, mic_ptr, ref_ptr, int(ld_in), out_ptr, int(ld_out), hops_ptr,
                                        int(max_hops), stream), self.h, 'aec_stream_push')
+
+    def delay_estimate(self, mic_ptr, ref_ptr, lengths, B, ld, max_lag, delay_ptr, curve_ptr, stream):
+        """lengths: host [B]; delay_ptr: device [B] int32; curve_ptr: device [B, max_lag + 1] or None"""
+        import numpy as np
+        lens = np.ascontiguousarray(lengths, dtype=np.int64)
+        check(self.lib.aec_delay_estimate(self.h, mic_ptr, ref_ptr, lens.ctypes.data, int(B), int(ld), int(max_lag),
+                                          delay_ptr, curve_ptr, stream), self.h, 'aec_delay_estimate')
+
+    def delay_apply(self, ref_ptr, lengths, B, ld, shift_ptr, out_ptr, ld_out, stream):
+        """shift_ptr: device [B] int32 frames (clamped to [0, 64] by the kernel)"""
+        import numpy as np
+        lens = np.ascontiguousarray(lengths, dtype=np.int64)
+        check(self.lib.aec_delay_apply(self.h, ref_ptr, lens.ctypes.data, int(B), int(ld), shift_ptr, out_ptr,
+                                       int(ld_out), stream), self.h, 'aec_delay_apply')
 
     def debug_copy(self, what, dst_ptr, n, stream):
         check(self.lib.aec_debug_copy(self.h, int(what), dst_ptr, int(n), stream), self.h, 'aec_debug_copy')

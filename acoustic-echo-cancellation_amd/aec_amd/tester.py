@@ -29,6 +29,9 @@ Extra flags (all optional):
 - `--nlms` puts the FD-NLMS stage in front of the post-filter;
 - `--kalman` puts the frequency-domain Kalman canceller there instead
   (`configs.kalman_conf`; the two flags exclude each other);
+- `--align MAX_LAG` estimates each utterance's far-end bulk delay over lags of
+  0 .. MAX_LAG frames and feeds the canceller the reference delayed by it
+  (`aec_amd.delay`; off by default);
 - `--streams` sets the utterances per GPU call;
 - `--device` picks the GPU (default: LOCAL_RANK, the rank's bound GPU);
 - `--gather` writes every file on rank 0 (waveforms gathered over RCCL).
@@ -79,6 +82,9 @@ def build_parser():
     lin.add_argument('--nlms', action='store_true', help='FD-NLMS linear AEC in front of the post-filter')
     lin.add_argument('--kalman', action='store_true',
                      help='frequency-domain Kalman linear AEC in front of the post-filter')
+    p.add_argument('--align', type=int, default=None, metavar='MAX_LAG',
+                   help='estimate the far-end bulk delay per utterance (lags 0..MAX_LAG frames, at most 63) and '
+                        'feed the aligned reference; off when not given')
     p.add_argument('--streams', type=int, default=64, help='utterances per GPU call')
     p.add_argument('--device', type=int, default=None, help='GPU index (default: LOCAL_RANK or 0)')
     p.add_argument('--gather', action='store_true',
@@ -132,11 +138,18 @@ class Tester(object):
         ERB = EquivalentRectangularBandwidth(erb_conf['nfreqs'], erb_conf['sample_rate'], erb_conf['total_erb_bands'],
                                              erb_conf['low_freq'], erb_conf['max_freq'])
         erb = torch.tensor(ERB.filters, dtype=torch.float32, device=device)
+        align = getattr(self.args, 'align', None)
+        if align is not None:
+            from .delay import align_ref, estimate_delay
 
         def enhance(mic, ref, near, lengths):
             lengths = np.asarray(lengths, np.int64).reshape(len(mic), 3)
             with torch.no_grad():
                 M, R, N = (torch.from_numpy(a).to(device, non_blocking=True) for a in (mic, ref, near))
+                if align is not None:
+                    # the overlap of mic and ref bounds the search; the shifted reference keeps its length
+                    both = np.minimum(lengths[:, 0], lengths[:, 1])
+                    R = align_ref(R, lengths[:, 1], estimate_delay(M, R, both, max_lag=align))
                 out, _ = net.forward_ragged(M, R, N, erb, lengths)
                 out = out.cpu().numpy()
             return [out[b, :256 * (int(n) // 256)] for b, n in enumerate(lengths[:, 0])]

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/aec_hip.h"
+#include "aec_delay.h"
 #include "aec_device.h"
 #include "aec_host.h"
 #include "aec_launch.h"
@@ -1010,6 +1011,50 @@ aec_status aec_adam_step_multi(aec_handle* h, float* const* params, const float*
             L.off[k + 1] = L.off[k] + sizes[i];
         }
         HIP_TRY(h, launch_adam_multi(L, beta1, beta2, eps, weight_decay, reinterpret_cast<hipStream_t>(stream)));
+    }
+    return AEC_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Far-end bulk delay (kernels in aec_delay.hip).  Stateless: the host lengths ride in the kernel
+// arguments, kDelayRows streams per launch, so the calls use none of the handle's workspace and
+// take no part in the ordering of its other calls (begin_call / end_call) or in the look-ahead.
+// ---------------------------------------------------------------------------
+aec_status aec_delay_estimate(aec_handle* h, const float* mic, const float* ref, const int64_t* lengths, int32_t B,
+                              int64_t ld, int32_t max_lag, int32_t* delay, float* curve, void* stream) {
+    if (!h) return AEC_ERR_INVALID_ARG;
+    const Check c = check_delay_args(true, mic, ref, delay, lengths, B, ld, max_lag, 0);
+    if (c.status != AEC_OK) return fail(h, c.status, c.why);
+    AEC_ON_DEVICE(h);
+    DelayArgs a{};
+    a.mic = mic; a.ref = ref; a.ld = ld; a.tables = reinterpret_cast<const float*>(h->d_tab);
+    a.delay = delay; a.curve = curve; a.max_lag = max_lag;
+    for (int32_t b0 = 0; b0 < B; b0 += kDelayRows) {
+        const int nb = std::min<int32_t>(kDelayRows, B - b0);
+        a.b0 = b0;
+        for (int i = 0; i < nb; ++i) a.len[i] = (int32_t)lengths[b0 + i];
+        HIP_TRY(h, launch_delay_estimate(a, nb, reinterpret_cast<hipStream_t>(stream)));
+    }
+    return AEC_OK;
+}
+
+aec_status aec_delay_apply(aec_handle* h, const float* ref, const int64_t* lengths, int32_t B, int64_t ld,
+                           const int32_t* shift, float* out, int64_t ld_out, void* stream) {
+    if (!h) return AEC_ERR_INVALID_ARG;
+    const Check c = check_delay_args(false, ref, shift, out, lengths, B, ld, 0, ld_out);
+    if (c.status != AEC_OK) return fail(h, c.status, c.why);
+    AEC_ON_DEVICE(h);
+    ShiftArgs a{};
+    a.ref = ref; a.ld = ld; a.shift = shift; a.out = out; a.ld_out = ld_out;
+    for (int32_t b0 = 0; b0 < B; b0 += kDelayRows) {
+        const int nb = std::min<int32_t>(kDelayRows, B - b0);
+        a.b0 = b0;
+        int64_t nmax = 0;
+        for (int i = 0; i < nb; ++i) {
+            a.len[i] = (int32_t)lengths[b0 + i];
+            nmax = std::max(nmax, lengths[b0 + i]);
+        }
+        HIP_TRY(h, launch_delay_apply(a, nb, nmax, reinterpret_cast<hipStream_t>(stream)));
     }
     return AEC_OK;
 }

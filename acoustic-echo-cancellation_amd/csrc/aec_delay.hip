@@ -1,0 +1,240 @@
+// aec_delay.hip — far-end bulk delay: estimator and shifter (include/aec_hip.h aec_delay_estimate /
+// aec_delay_apply).  No reference counterpart: the reference has no linear stage.
+//
+// Estimator, per stream (frames as everywhere here: Hann-windowed x[256(t-1) : 256(t+1)], zero
+// outside [0, n), T = n/256 + 1; no normaliser: its constant lands in DC only, which is left out),
+// bins k = 1..255, lags d = 0..max_lag, R[t] = 0 for t < 0:
+//   C_k[d] = sum_t M[t,k] conj(R[t-d,k])     P_k[d] = sum_t |R[t-d,k]|^2
+//   S[d]   = sum_k |C_k[d]|^2 / (P_k[d] + 1e-6)          delay = the smallest d that maximises S
+//
+// One block of four waves per stream walks it once in chunks of CHUNK frames, two phases per chunk:
+//   transform  wave w < 2 CHUNK/4: signal w / (CHUNK/4) (mic, ref), frames 4 (w % (CHUNK/4)) .. +3
+//              of the chunk, one 16-lane group per frame (aec_stft.h / aec_fft.h).  A mic row stays
+//              in the group's own LDS scratch; a ref row goes into the ring, slot = frame mod rows.
+//   correlate  thread k = bin k.  The ring keeps the last CAP - 1 far-end rows before the chunk and
+//              the chunk's own, so lane k reads each row once (its own column: consecutive lanes,
+//              consecutive 8-byte words, no bank conflict) and pairs it with every mic frame of the
+//              chunk it belongs to: acc[t - r] += M[t] conj(R[r]), one complex accumulator per lag
+//              in registers, every index static.
+// P_k[d] has no accumulator per lag: `head` sums |R[r]|^2 over r <= T-1-max_lag as the rows pass,
+// and the last max_lag rows are still in the ring at the end, so P[max_lag] = head and
+// P[d] = P[d+1] + |R[T-1-d]|^2 (sums of non-negative terms only: no cancellation).
+// The order of every sum depends on the stream's own T and max_lag alone, so a stream's curve does
+// not depend on the batch, its row or the other rows.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "aec_delay.h"
+#include "aec_fft.h"
+#include "aec_stft.h"
+#include "aec_tables.h"
+
+namespace aec {
+
+// acc += m conj(r) as two packed FMAs (one VALU issue per pair of lanes' products, as the FFT core
+// of aec_fft.h): (m.x, m.y) r.x, then mi r.y with mi = -i m = (m.y, -m.x); r's half is picked by op_sel
+__device__ __forceinline__ void cmac_conj(pf2& acc, pf2 m, pf2 mi, pf2 r) {
+    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[1,0,1]" : "+v"(acc) : "v"(m), "v"(r));
+    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "+v"(acc) : "v"(mi), "v"(r));
+}
+
+template <int CAP, int CHUNK>
+struct DelayCfg {
+    static_assert(CHUNK % 4 == 0 && CHUNK >= 4 && CHUNK <= 8, "a wave transforms 4 frames; 4 waves, 2 signals");
+    static constexpr int kTW = CHUNK / 4;             // transform waves per signal
+    static constexpr int kRows = CAP - 1 + CHUNK;     // ring rows of 256 float2
+    static constexpr size_t kBytes =
+        (258 * 2 + 256 * 2 + 512 + (size_t)2 * kTW * kWaveFloats + (size_t)kRows * 512) * sizeof(float);
+    static_assert(kBytes <= 160 * 1024, "LDS");
+    static_assert(2 * kTW * kWaveFloats >= 5 * CAP, "the final reduction reuses the wave regions");
+};
+
+template <int CAP, int CHUNK>
+__global__ __launch_bounds__(256, 1) void delay_estimate_kernel(DelayArgs p) {
+    using Cfg = DelayCfg<CAP, CHUNK>;
+    constexpr int TW = Cfg::kTW, NR = Cfg::kRows;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float2* sTw512 = reinterpret_cast<float2*>(smem);                 // 258
+    float2* sTwT = sTw512 + 258;                                      // 256
+    float* sHann = reinterpret_cast<float*>(sTwT + 256);              // 512
+    float* sWave = sHann + 512;                                       // 2 TW * kWaveFloats
+    float2* sRing = reinterpret_cast<float2*>(sWave + 2 * TW * kWaveFloats);   // NR * 256
+
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int gg = lane >> 4, lb = lane & 15;
+    const DevTables* tb = reinterpret_cast<const DevTables*>(p.tables);
+    sTwT[tid] = tb->twT[tid];
+    sTw512[tid] = tb->tw512[tid];
+    if (tid < 2) sTw512[256 + tid] = tb->tw512[256 + tid];
+    sHann[tid] = tb->hann[tid];
+    sHann[tid + 256] = tb->hann[tid + 256];
+    {   // frames before the stream's first are zero rows
+        float4* r4 = reinterpret_cast<float4*>(sRing);
+        for (int i = tid; i < NR * 128; i += 256) r4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    const int b = p.b0 + (int)blockIdx.x;
+    const int n = p.len[blockIdx.x];
+    const int T = n / kHop + 1;
+    const int max_lag = p.max_lag;
+
+    const bool tw = wave < 2 * TW;                                    // this wave transforms
+    const int sig = wave / TW, sub = wave % TW;
+    const float* row = (sig == 0 ? p.mic : p.ref) + (int64_t)b * p.ld;
+    const bool al = (reinterpret_cast<uintptr_t>(row) & 15) == 0;
+    float* wr = sWave + (tw ? wave : 0) * kWaveFloats;
+    float* scr = wr + gg * kGroupFloats;
+    float4 pf[kWavePf];
+    if (tw) wave_prefetch(pf, row, n, 4 * sub, lane, al);
+    __syncthreads();
+
+    const int k = tid;
+    pf2 acc[CAP];
+#pragma unroll
+    for (int d = 0; d < CAP; ++d) acc[d] = pf2{0.f, 0.f};
+    float head = 0.f;
+    int s0 = 0;                                                       // ring slot of frame t0
+    for (int t0 = 0; t0 < T; t0 += CHUNK) {
+        if (tw) {
+            asm volatile("" ::: "memory");                            // keep the table reads inside the loop
+            const int wt = t0 + 4 * sub;
+            wave_commit(wr, pf, 0.f, n, wt, lane);
+            if (t0 + CHUNK < T) wave_prefetch(pf, row, n, wt + CHUNK, lane, al);
+            wave_fence();
+            float2 v[16];
+            load_frame(v, wr, sHann, gg, lb);
+            wave_fence();                                             // samples read before scratch reuse
+            fft256<false>(v, lb, scr, sTwT);
+            float2 xa[8], xb[8], x128;
+            rfft_unpack(v, lb, sTw512, xa, xb, x128);
+            int slot = s0 + 4 * sub + gg;
+            slot -= slot >= NR ? NR : 0;
+            float2* dst = sig == 0 ? reinterpret_cast<float2*>(scr) : sRing + slot * 256;
+#pragma unroll
+            for (int m = 0; m < 8; ++m) {
+                const int kk = lb + 16 * m;
+                dst[kk] = xa[m];                                      // slot 0 holds DC: never read
+                if (kk) dst[256 - kk] = xb[m];
+            }
+            if (lb == 0) dst[128] = x128;
+        }
+        __syncthreads();
+        {
+            pf2 M[CHUNK], Mi[CHUNK];                                  // M and -i M = (M.y, -M.x)
+            static_for<0, CHUNK>([&](auto ii) {
+                constexpr int i = decltype(ii)::value;
+                float2 mv = reinterpret_cast<const float2*>(sWave + (i / 4) * kWaveFloats + (i % 4) * kGroupFloats)[k];
+                mv = csel(t0 + i < T, mv, make_float2(0.f, 0.f));
+                M[i] = pf2{mv.x, mv.y};
+                Mi[i] = pf2{mv.y, -mv.x};
+            });
+            // row j of the pass is frame r = t0 + CHUNK-1 - j; it meets mic frame t0 + i at lag j - (CHUNK-1) + i
+            static_for<0, CAP + CHUNK - 1>([&](auto jj) {
+                constexpr int j = decltype(jj)::value;
+                if (j - (CHUNK - 1) <= max_lag) {                     // else every lag it serves is past max_lag
+                    int slot = s0 + (CHUNK - 1 - j);
+                    slot += slot < 0 ? NR : 0;
+                    slot -= slot >= NR ? NR : 0;
+                    const float2 rv = sRing[slot * 256 + k];
+                    const pf2 rp = pf2{rv.x, rv.y};
+                    if constexpr (j < CHUNK) {
+                        if (t0 + (CHUNK - 1 - j) <= T - 1 - max_lag) head = fmaf(rv.x, rv.x, fmaf(rv.y, rv.y, head));
+                    }
+                    static_for<0, CHUNK>([&](auto ii) {
+                        constexpr int i = decltype(ii)::value;
+                        constexpr int d = j - (CHUNK - 1) + i;
+                        if constexpr (d >= 0 && d < CAP) cmac_conj(acc[d], M[i], Mi[i], rp);
+                    });
+                }
+            });
+        }
+        __syncthreads();                                              // rows consumed
+        s0 += CHUNK;
+        s0 -= s0 >= NR ? NR : 0;
+    }
+
+    // S[d] = sum_k |C_k[d]|^2 / (P_k[d] + eps), from the largest lag down so P grows by one row per lag
+    float* sRed = sWave;                                              // [CAP][4]
+    float* sCurve = sWave + 4 * CAP;                                  // [CAP]
+    float pw = head;
+    static_for<0, CAP>([&](auto dd) {
+        constexpr int d = CAP - 1 - decltype(dd)::value;
+        if (d <= max_lag) {
+            if (d < max_lag && T - 1 - d >= 0) {
+                const float2 rv = sRing[((T - 1 - d) % NR) * 256 + k];
+                pw = fmaf(rv.x, rv.x, fmaf(rv.y, rv.y, pw));
+            }
+            float s = 0.f;
+            if (k >= 1 && d < T) s = fmaf(acc[d].x, acc[d].x, acc[d].y * acc[d].y) / (pw + 1e-6f);
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+            if (lane == 0) sRed[4 * d + wave] = s;
+        }
+    });
+    __syncthreads();
+    if (tid <= max_lag) {
+        const float s = (sRed[4 * tid] + sRed[4 * tid + 1]) + (sRed[4 * tid + 2] + sRed[4 * tid + 3]);
+        sCurve[tid] = s;
+        if (p.curve) p.curve[(int64_t)b * (max_lag + 1) + tid] = s;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int best = 0;
+        float bv = sCurve[0];
+        for (int d = 1; d <= max_lag; ++d)
+            if (sCurve[d] > bv) {
+                bv = sCurve[d];
+                best = d;
+            }
+        p.delay[b] = best;
+    }
+}
+
+// out[b, i] = i >= 256 s_b ? ref[b, i - 256 s_b] : 0 for i < len[b]; lane i of a wave touches sample
+// i of a run of 64 on both sides (dword accesses: coalesced for any ld, ld_out and alignment)
+__global__ __launch_bounds__(256) void delay_apply_kernel(ShiftArgs p) {
+    const int b = p.b0 + (int)blockIdx.y;
+    const int64_t n = p.len[blockIdx.y];
+    int s = p.shift[b];
+    s = s < 0 ? 0 : (s > kDelayMaxShift ? kDelayMaxShift : s);
+    const int64_t off = (int64_t)kHop * s;
+    const float* __restrict__ src = p.ref + (int64_t)b * p.ld;
+    float* __restrict__ dst = p.out + (int64_t)b * p.ld_out;
+    const int64_t i0 = (int64_t)blockIdx.x * 1024 + threadIdx.x;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int64_t i = i0 + 256 * u;
+        if (i < n) dst[i] = i >= off ? src[i - off] : 0.f;
+    }
+}
+
+template <int CAP, int CHUNK>
+static hipError_t launch_delay_cap(const DelayArgs& a, int nb, hipStream_t st) {
+    constexpr size_t lds = DelayCfg<CAP, CHUNK>::kBytes;
+    // > 64 KiB of LDS: opt in once per instantiation
+    static const hipError_t attr =
+        hipFuncSetAttribute(reinterpret_cast<const void*>(delay_estimate_kernel<CAP, CHUNK>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (attr != hipSuccess) return attr;
+    hipLaunchKernelGGL((delay_estimate_kernel<CAP, CHUNK>), dim3(nb), dim3(256), lds, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_delay_estimate(const DelayArgs& a, int nb, hipStream_t st) {
+    if (nb <= 0) return hipSuccess;
+    if (nb > kDelayRows || a.max_lag < 0 || a.max_lag > kDelayMaxLag) return hipErrorInvalidValue;
+    // lag capacity 16 / 32 / 48 / 64: a short search does not carry 64 lags of accumulators; the 64-lag
+    // ring leaves LDS for two transform waves (chunks of 4 frames), the others for four (8 frames)
+    if (a.max_lag < 16) return launch_delay_cap<16, 8>(a, nb, st);
+    if (a.max_lag < 32) return launch_delay_cap<32, 8>(a, nb, st);
+    if (a.max_lag < 48) return launch_delay_cap<48, 8>(a, nb, st);
+    return launch_delay_cap<64, 4>(a, nb, st);
+}
+
+hipError_t launch_delay_apply(const ShiftArgs& a, int nb, int64_t nmax, hipStream_t st) {
+    if (nb <= 0 || nmax <= 0) return hipSuccess;
+    if (nb > kDelayRows) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(delay_apply_kernel, dim3((unsigned)((nmax + 1023) / 1024), nb), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+}  // namespace aec

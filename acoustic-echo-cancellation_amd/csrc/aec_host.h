@@ -271,6 +271,32 @@ inline Check check_stream_push(int32_t max_hops, int64_t ld_in, int64_t ld_out) 
     return {};
 }
 
+// aec_delay_estimate (estimate = true: in0 = mic, in1 = ref, out = delay; max_lag in [0, 63]) and
+// aec_delay_apply (in0 = ref, in1 = shift, out = the shifted rows; ld_out must hold the longest
+// row, and the shift cannot run in place).  *nmax (optional) receives the longest length.  The
+// kernels address a row through 32-bit byte offsets, hence the length limit (9 hours at 16 kHz).
+constexpr int64_t kDelayMaxLen = ((int64_t)1 << 29) - 4096;
+inline Check check_delay_args(bool estimate, const void* in0, const void* in1, const void* out, const int64_t* lengths,
+                              int32_t B, int64_t ld, int32_t max_lag, int64_t ld_out, int64_t* nmax = nullptr) {
+    if (!in0 || !in1 || !out) return {AEC_ERR_INVALID_ARG, estimate ? "null mic / ref / delay" : "null ref / shift / out"};
+    if (!lengths) return {AEC_ERR_INVALID_ARG, "null lengths"};
+    if (B < 1) return {AEC_ERR_INVALID_ARG, "B must be >= 1"};
+    if (estimate && (max_lag < 0 || max_lag > 63)) return {AEC_ERR_INVALID_ARG, "max_lag out of [0, 63]"};
+    int64_t m = 0;
+    for (int b = 0; b < B; ++b) {
+        const int64_t n = lengths[b];
+        if (n < 1 || n > ld) return {AEC_ERR_INVALID_ARG, "length out of [1, ld]"};
+        if (n > kDelayMaxLen) return {AEC_ERR_UNSUPPORTED, "stream longer than 2^29 - 4096 samples"};
+        m = n > m ? n : m;
+    }
+    if (!estimate) {
+        if (ld_out < m) return {AEC_ERR_INVALID_ARG, "ld_out below the longest length"};
+        if (out == in0) return {AEC_ERR_INVALID_ARG, "out must not be ref (the shift cannot run in place)"};
+    }
+    if (nmax) *nmax = m;
+    return {};
+}
+
 // dst[B][4] = (mic, ref, near, 0) lengths as the kernels read them (normaliser
 // + zero padding); a signal that is not given takes mic's length
 inline void fill_slen(int32_t* dst, const int64_t* lengths3, int32_t B, int nsig) {

@@ -207,6 +207,42 @@ aec_status aec_stream_step(aec_handle* h, const float* mic, const float* ref, in
 aec_status aec_stream_push(aec_handle* h, const float* mic, const float* ref, int64_t ld_in,
                            float* out, int64_t ld_out, const int32_t* hops, int32_t max_hops, void* stream);
 
+/* Far-end bulk delay (no reference counterpart).  The cancellers
+ * see nlms_taps <= 8 frames (128 ms) of far-end history; play-out and capture
+ * buffering put 50 .. 500 ms between ref and its echo in mic.  aec_delay_estimate
+ * finds that offset in whole frames, aec_delay_apply delays ref by it, and the
+ * canceller then runs unchanged on the aligned reference.
+ * With the frames of aec_process (Hann-windowed x[256(t-1) : 256(t+1)], zero
+ * outside [0, n), T = n/256 + 1, no normaliser), bins k = 1..255, lags
+ * d = 0..max_lag and R[t] = 0 for t < 0:
+ *   C_k[d] = sum_t M[t,k] conj(R[t-d,k])      P_k[d] = sum_t |R[t-d,k]|^2
+ *   S[d]   = sum_k |C_k[d]|^2 / (P_k[d] + 1e-6)
+ *   delay  = the smallest d that maximises S  (an all-zero curve: 0)
+ * S[d] is the echo energy a single tap at lag d explains; the peak sits up to
+ * two frames after the first echo energy.
+ *   mic, ref : device [B, ld] float32
+ *   lengths  : host [B] int64, each in [1, ld] (and at most 2^29 - 4096:
+ *              AEC_ERR_UNSUPPORTED beyond)
+ *   max_lag  : 0 .. 63 frames
+ *   delay    : device [B] int32
+ *   curve    : device [B, max_lag + 1] float32 receives S, or NULL
+ * A stream's curve does not depend on B, on its row or on the other rows.
+ *
+ * aec_delay_apply: out[b, i] = i >= 256 s_b ? ref[b, i - 256 s_b] : 0 for
+ * i < lengths[b], s_b = shift[b] clamped to [0, 64] by the kernel; nothing is
+ * written beyond lengths[b].
+ *   shift    : DEVICE [B] int32, frames (e.g. aec_delay_estimate's delay, so a
+ *              caller need not synchronise between the two calls)
+ *   out      : device [B, ld_out] float32, ld_out >= the longest length; not ref
+ * Neither call needs weights or the ERB matrix, touches streaming or training
+ * state, or consumes a look-ahead.  AEC_ERR_INVALID_ARG (text in
+ * aec_last_error): a null pointer (curve excepted), B < 1, a length outside
+ * [1, ld], max_lag outside [0, 63], ld_out below the longest length, out == ref. */
+aec_status aec_delay_estimate(aec_handle* h, const float* mic, const float* ref, const int64_t* lengths,
+                              int32_t B, int64_t ld, int32_t max_lag, int32_t* delay, float* curve, void* stream);
+aec_status aec_delay_apply(aec_handle* h, const float* ref, const int64_t* lengths, int32_t B, int64_t ld,
+                           const int32_t* shift, float* out, int64_t ld_out, void* stream);
+
 /* Debug / parity: copy an intermediate of the LAST aec_process call into the
  * device buffer dst ([B, T_max, 32] float32, frames beyond a stream's T left
  * unspecified).  Requires aec_set_debug(h, 1) before that call.
