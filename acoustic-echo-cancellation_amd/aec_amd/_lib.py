@@ -28,6 +28,7 @@ EXPORTS = ('aec_weights_count', 'aec_create', 'aec_set_weights', 'aec_set_erb', 
            'aec_prepare', 'aec_prepare_siglens', 'aec_process_prepared',
            'aec_stream_open', 'aec_stream_reset', 'aec_stream_step', 'aec_stream_push',
            'aec_delay_estimate', 'aec_delay_apply',
+           'aec_delay_track_open', 'aec_delay_track_reset', 'aec_delay_track_push',
            'aec_set_debug', 'aec_debug_copy', 'aec_profile_enable', 'aec_profile_read',
            'aec_erb_tables_check', 'aec_num_frames', 'aec_out_len', 'aec_last_error', 'aec_destroy',
            'aec_set_weights_device', 'aec_train_forward', 'aec_train_backward', 'aec_train_generation',
@@ -49,6 +50,12 @@ class CrnConfig(ctypes.Structure):
                 ('masking_mode', ctypes.c_int32), ('dtype', ctypes.c_int32),
                 ('nlms_taps', ctypes.c_int32), ('nlms_mu', ctypes.c_float), ('nlms_beta', ctypes.c_float),
                 ('nlms_delta', ctypes.c_float)]
+
+
+class DelayTrackConfig(ctypes.Structure):
+    """aec_delay_track_config (include/aec_hip.h)."""
+    _fields_ = [('max_lag', ctypes.c_int32), ('period', ctypes.c_int32), ('hold', ctypes.c_int32),
+                ('lead', ctypes.c_int32), ('forget', ctypes.c_float), ('ratio', ctypes.c_float)]
 
 
 class AecConfig(ctypes.Structure):
@@ -112,6 +119,13 @@ def load():
         lib.aec_delay_estimate.restype = ctypes.c_int
         lib.aec_delay_apply.argtypes = [P, P, P, ctypes.c_int32, ctypes.c_int64, P, P, ctypes.c_int64, P]
         lib.aec_delay_apply.restype = ctypes.c_int
+    if LIB_PATH == _DEFAULT_LIB or hasattr(lib, 'aec_delay_track_open'):   # absent from an older A/B build
+        lib.aec_delay_track_open.argtypes = [P, ctypes.c_int32, ctypes.POINTER(DelayTrackConfig)]
+        lib.aec_delay_track_open.restype = ctypes.c_int
+        lib.aec_delay_track_reset.argtypes = [P, ctypes.c_int32, P]
+        lib.aec_delay_track_reset.restype = ctypes.c_int
+        lib.aec_delay_track_push.argtypes = [P, P, P, ctypes.c_int64, P, ctypes.c_int64, P, ctypes.c_int32, P, P, P]
+        lib.aec_delay_track_push.restype = ctypes.c_int
     lib.aec_set_debug.argtypes = [P, ctypes.c_int32]
     lib.aec_set_debug.restype = ctypes.c_int
     lib.aec_debug_copy.argtypes = [P, ctypes.c_int32, P, ctypes.c_size_t, P]
@@ -312,6 +326,21 @@ class Handle:
         lens = np.ascontiguousarray(lengths, dtype=np.int64)
         check(self.lib.aec_delay_apply(self.h, ref_ptr, lens.ctypes.data, int(B), int(ld), shift_ptr, out_ptr,
                                        int(ld_out), stream), self.h, 'aec_delay_apply')
+
+    def delay_track_open(self, B, max_lag, forget, period, hold, ratio, lead):
+        cfg = DelayTrackConfig(int(max_lag), int(period), int(hold), int(lead), float(forget), float(ratio))
+        check(self.lib.aec_delay_track_open(self.h, int(B), ctypes.byref(cfg)), self.h, 'aec_delay_track_open')
+
+    def delay_track_reset(self, b, stream):
+        check(self.lib.aec_delay_track_reset(self.h, int(b), stream), self.h, 'aec_delay_track_reset')
+
+    def delay_track_push(self, mic_ptr, ref_ptr, ld_in, out_ptr, ld_out, hops_ptr, max_hops, delay_ptr, curve_ptr,
+                         stream):
+        """hops_ptr: device [B] int32 or None; delay_ptr: device [B] int32 or None; curve_ptr: device
+        [B, max_lag + 1] or None"""
+        check(self.lib.aec_delay_track_push(self.h, mic_ptr, ref_ptr, int(ld_in), out_ptr, int(ld_out), hops_ptr,
+                                            int(max_hops), delay_ptr, curve_ptr, stream), self.h,
+              'aec_delay_track_push')
 
     def debug_copy(self, what, dst_ptr, n, stream):
         check(self.lib.aec_debug_copy(self.h, int(what), dst_ptr, int(n), stream), self.h, 'aec_debug_copy')

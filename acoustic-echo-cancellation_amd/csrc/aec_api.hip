@@ -118,6 +118,11 @@ struct aec_handle {
     float* d_state = nullptr;
     int32_t stream_B = 0;
     int64_t stream_stride = 0;
+    // streaming delay tracker (aec_delay_track_*): per-stream state [track_B][track_stride]
+    float* d_track = nullptr;
+    int32_t track_B = 0;
+    int64_t track_stride = 0;
+    aec_delay_track_config track_cfg{};
     // training (aec_train_*): state of the last aec_train_forward, read by aec_train_backward
     float* d_th = nullptr;       // [B][T][32] GRU outputs
     float* d_tloss = nullptr;    // [B] per-row loss
@@ -1082,10 +1087,63 @@ void aec_destroy(aec_handle* h) {
     (void)hipFree(h->d_mom); (void)hipFree(h->d_cvals); (void)hipFree(h->d_lists);
     (void)hipFree(h->d_feats); (void)hipFree(h->d_est); (void)hipFree(h->d_dbg); (void)hipFree(h->d_spec);
     (void)hipFree(h->d_state); (void)hipFree(h->d_rows); (void)hipFree(h->d_progress);
+    (void)hipFree(h->d_track);
     if (h->h_pipe_err) (void)hipHostFree(h->h_pipe_err);
     (void)hipFree(h->d_th); (void)hipFree(h->d_tloss); (void)hipFree(h->d_rec); (void)hipFree(h->d_dg);
     (void)hipFree(h->d_part); (void)hipFree(h->d_scan);
     delete h;
+}
+
+// ---------------------------------------------------------------------------
+// The far-end delay while streaming (kernel in aec_delay.hip, checks in aec_host.h).  The state
+// belongs to the tracker alone: the calls use none of the handle's workspace, take no part in the
+// ordering of its other calls and need neither weights nor the ERB matrix.
+// ---------------------------------------------------------------------------
+aec_status aec_delay_track_open(aec_handle* h, int32_t B, const aec_delay_track_config* cfg) {
+    if (!h) return AEC_ERR_INVALID_ARG;
+    if (!cfg) return fail(h, AEC_ERR_INVALID_ARG, "null config");
+    const Check c = check_delay_track_open(B, cfg->max_lag, cfg->period, cfg->hold, cfg->lead, cfg->forget, cfg->ratio);
+    if (c.status != AEC_OK) return fail(h, c.status, c.why);
+    AEC_ON_DEVICE(h);
+    HIP_TRY(h, hipDeviceSynchronize());   // a previous state may still be in use
+    if (h->d_track) { HIP_TRY(h, hipFree(h->d_track)); h->d_track = nullptr; }
+    h->track_B = 0;
+    const int64_t stride = delay_track_state_floats(delay_track_cap(cfg->max_lag));
+    HIP_TRY(h, hipMalloc(&h->d_track, (size_t)B * stride * sizeof(float)));
+    HIP_TRY(h, hipMemset(h->d_track, 0, (size_t)B * stride * sizeof(float)));
+    h->track_B = B;
+    h->track_stride = stride;
+    h->track_cfg = *cfg;
+    return AEC_OK;
+}
+
+aec_status aec_delay_track_reset(aec_handle* h, int32_t b, void* stream) {
+    if (!h) return AEC_ERR_INVALID_ARG;
+    if (!h->d_track) return fail(h, AEC_ERR_INVALID_ARG, "aec_delay_track_open first");
+    if (b < -1 || b >= h->track_B) return fail(h, AEC_ERR_INVALID_ARG, "stream index out of range");
+    AEC_ON_DEVICE(h);
+    const int64_t first = b < 0 ? 0 : b, count = b < 0 ? h->track_B : 1;
+    HIP_TRY(h, hipMemsetAsync(h->d_track + first * h->track_stride, 0, (size_t)count * h->track_stride * sizeof(float),
+                              reinterpret_cast<hipStream_t>(stream)));
+    return AEC_OK;
+}
+
+aec_status aec_delay_track_push(aec_handle* h, const float* mic, const float* ref, int64_t ld_in, float* ref_out,
+                                int64_t ld_out, const int32_t* hops, int32_t max_hops, int32_t* delay, float* curve,
+                                void* stream) {
+    if (!h) return AEC_ERR_INVALID_ARG;
+    const Check c = check_delay_track(h->d_track != nullptr, mic, ref, ref_out, max_hops, ld_in, ld_out);
+    if (c.status != AEC_OK) return fail(h, c.status, c.why);
+    AEC_ON_DEVICE(h);
+    TrackArgs a{};
+    a.mic = mic; a.ref = ref; a.ld_in = ld_in; a.ref_out = ref_out; a.ld_out = ld_out;
+    a.hops = hops; a.max_hops = max_hops; a.delay = delay; a.curve = curve;
+    a.state = h->d_track; a.state_stride = h->track_stride;
+    a.tables = reinterpret_cast<const float*>(h->d_tab);
+    a.max_lag = h->track_cfg.max_lag; a.period = h->track_cfg.period; a.hold = h->track_cfg.hold;
+    a.lead = h->track_cfg.lead; a.forget = h->track_cfg.forget; a.ratio = h->track_cfg.ratio;
+    HIP_TRY(h, launch_delay_track(a, h->track_B, reinterpret_cast<hipStream_t>(stream)));
+    return AEC_OK;
 }
 
 }  // extern "C"

@@ -207,6 +207,262 @@ __global__ __launch_bounds__(256) void delay_apply_kernel(ShiftArgs p) {
     }
 }
 
+// ---------------------------------------------------------------------------
+// The streaming tracker (include/aec_hip.h aec_delay_track_*): the estimator above
+// made recursive, C_k[d] = lam C_k[d] + M[t] conj(R[t-d]) and q[t] = lam q[t-1] + |R[t]|^2 with
+// P_k[d] = q_k[t-d], evaluated every `period` hops, and the reference hop t - max(target - lead, 0)
+// copied out at every hop.  One block of four waves per stream advances it by a packet of hops:
+//   transform  as above, chunks of 8 hops: waves 0, 1 the mic, waves 2, 3 the ref, one 16-lane
+//              group per frame; the hop before the packet's first is the state's `prev` row, patched
+//              into the staged hops where the buffer load returned its out-of-range zero.  Both
+//              rows of a frame stay in the group's own LDS scratch.
+//   correlate  thread k = bin k, the hops of the chunk one after another: the new far-end row and
+//              q go into the state's rings, the max_lag older rows come back from the R ring in
+//              HBM in batches of 16 independent 8-byte loads (lane k its own column: coalesced),
+//              and each lag's accumulator (in registers for the whole packet) is scaled by lam in
+//              a multiply of its own and then takes cmac_conj.  Only the current row is read from
+//              LDS: a thread reads back from the ring exactly what it stored there, so no barrier
+//              orders the ring, and staging CAP rows in LDS (128 KiB at 64 lags) would buy 7 of 64
+//              row reads per hop at best.  The q ring is read on evaluation hops only.
+//   evaluate   the end phase above on hops with (t + 1) % period == 0, then the first maximiser
+//              by a shuffle reduction every wave runs for itself, so all threads hold the decision.
+// A hop's arithmetic is the same wherever the packet boundaries fall, and every sum's order is
+// fixed by the lag capacity alone: results do not depend on B, the row, the strides or the packets.
+// ---------------------------------------------------------------------------
+template <int CAP>
+struct TrackCfg {
+    static constexpr int kChunk = 8;                  // hops per transform phase: 2 waves x 4 frames per signal
+    static constexpr size_t kBytes = (258 * 2 + 256 * 2 + 512 + (size_t)4 * kWaveFloats + 5 * CAP) * sizeof(float);
+    static_assert(CAP % 16 == 0 && CAP <= 64, "lags go in batches of 16; a wave finds the maximiser of <= 64");
+    static_assert(kBytes <= 64 * 1024, "LDS without opting in");
+};
+
+template <int CAP>
+__global__ __launch_bounds__(256, 1) void delay_track_kernel(TrackArgs p) {
+    constexpr int CH = TrackCfg<CAP>::kChunk;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float2* sTw512 = reinterpret_cast<float2*>(smem);                 // 258
+    float2* sTwT = sTw512 + 258;                                      // 256
+    float* sHann = reinterpret_cast<float*>(sTwT + 256);              // 512
+    float* sWave = sHann + 512;                                       // 4 * kWaveFloats
+    float* sRed = sWave + 4 * kWaveFloats;                            // [CAP][4]
+    float* sCurve = sRed + 4 * CAP;                                   // [CAP]
+
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int gg = lane >> 4, lb = lane & 15;
+    const int64_t b = blockIdx.x;
+    int cnt = p.max_hops;
+    if (p.hops) {
+        const int h = p.hops[b];
+        cnt = h < 0 ? 0 : (h > p.max_hops ? p.max_hops : h);
+    }
+    if (cnt == 0) return;                                             // nothing of this stream changes
+
+    const DevTables* tb = reinterpret_cast<const DevTables*>(p.tables);
+    sTwT[tid] = tb->twT[tid];
+    sTw512[tid] = tb->tw512[tid];
+    if (tid < 2) sTw512[256 + tid] = tb->tw512[256 + tid];
+    sHann[tid] = tb->hann[tid];
+    sHann[tid + 256] = tb->hann[tid + 256];
+
+    float* st = p.state + b * p.state_stride;
+    float2* gC = reinterpret_cast<float2*>(st);                       // [CAP][256]
+    float2* gR = gC + CAP * 256;                                      // [CAP][256]
+    float* gQ = reinterpret_cast<float*>(gR + CAP * 256);             // [CAP][256]
+    float* gSamp = gQ + CAP * 256;                                    // [64][256]
+    float* gPrev = gSamp + 64 * 256;                                  // [2][256]
+    float* gCurve = gPrev + 512;                                      // [64]
+    int32_t* gHdr = reinterpret_cast<int32_t*>(gCurve + 64);          // t, target, cand, run
+    const int t0 = gHdr[0];
+    int target = gHdr[1], cand = gHdr[2], run = gHdr[3];
+    const int max_lag = p.max_lag, period = p.period;
+
+    const int sig = wave >> 1, sub = wave & 1;                        // this wave's signal and half of a chunk
+    const float* microw = p.mic + b * p.ld_in;
+    const float* refrow = p.ref + b * p.ld_in;
+    const float* row = sig == 0 ? microw : refrow;
+    const bool al = (reinterpret_cast<uintptr_t>(row) & 15) == 0;
+    const int n = cnt * kHop;
+    float* wr = sWave + wave * kWaveFloats;
+    float* scr = wr + gg * kGroupFloats;
+    const float4 prev = *reinterpret_cast<const float4*>(gPrev + sig * 256 + 4 * lane);   // hop t0 - 1
+    float4 pf[kWavePf];
+    if (4 * sub < cnt) wave_prefetch(pf, row, n, 4 * sub, lane, al);
+
+    const int k = tid;
+    pf2 acc[CAP];
+    static_for<0, CAP / 16>([&](auto gi) {
+        constexpr int g = decltype(gi)::value;
+        if (16 * g <= max_lag) {
+#pragma unroll
+            for (int u = 0; u < 16; ++u) {
+                const float2 c = gC[(16 * g + u) * 256 + k];
+                acc[16 * g + u] = pf2{c.x, c.y};
+            }
+        } else {
+#pragma unroll
+            for (int u = 0; u < 16; ++u) acc[16 * g + u] = pf2{0.f, 0.f};
+        }
+    });
+    const pf2 lam = pf2{p.forget, p.forget};
+    int slot = t0 % CAP;                                              // ring slot of the hop at hand
+    float q = gQ[(slot ? slot - 1 : CAP - 1) * 256 + k];              // q[t0 - 1]
+    int ph = t0 % period;                                             // hop t evaluates when t % period == period - 1
+    float sLast = tid < 64 ? gCurve[tid] : 0.f;
+    __syncthreads();                                                  // tables
+
+    for (int c0 = 0; c0 < cnt; c0 += CH) {
+        const int wt = c0 + 4 * sub;                                  // this wave's first frame, packet-relative
+        if (wt < cnt) {
+            asm volatile("" ::: "memory");                            // keep the table reads inside the loop
+            wave_commit(wr, pf, 0.f, n, wt, lane);
+            if (wt == 0) *reinterpret_cast<float4*>(wr + 4 * lane) = prev;
+            if (wt + CH < cnt) wave_prefetch(pf, row, n, wt + CH, lane, al);
+            wave_fence();
+            float2 v[16];
+            load_frame(v, wr, sHann, gg, lb);
+            wave_fence();                                             // samples read before scratch reuse
+            fft256<false>(v, lb, scr, sTwT);
+            float2 xa[8], xb[8], x128;
+            rfft_unpack(v, lb, sTw512, xa, xb, x128);
+            float2* dst = reinterpret_cast<float2*>(scr);
+#pragma unroll
+            for (int m = 0; m < 8; ++m) {
+                const int kk = lb + 16 * m;
+                dst[kk] = xa[m];                                      // slot 0 holds DC: left out of S
+                if (kk) dst[256 - kk] = xb[m];
+            }
+            if (lb == 0) dst[128] = x128;
+        }
+        __syncthreads();
+        const int nch = cnt - c0 < CH ? cnt - c0 : CH;
+        for (int i = 0; i < nch; ++i) {
+            const int j = c0 + i;                                     // hop t = t0 + j
+            // the aligned hop: out of the packet, or out of the sample ring when it lies before it
+            int s = target - p.lead;
+            s = s < 0 ? 0 : s;
+            const int src = j - s;
+            float ao = 0.f;
+            if (src >= 0) ao = refrow[(int64_t)src * kHop + k];
+            else if (t0 + src >= 0) ao = gSamp[((t0 + src) & 63) * 256 + k];
+
+            const float2 mv = reinterpret_cast<const float2*>(sWave + (i >> 2) * kWaveFloats + (i & 3) * kGroupFloats)[k];
+            const float2 rv =
+                reinterpret_cast<const float2*>(sWave + (2 + (i >> 2)) * kWaveFloats + (i & 3) * kGroupFloats)[k];
+            q = fmaf(p.forget, q, fmaf(rv.x, rv.x, rv.y * rv.y));
+            gR[slot * 256 + k] = rv;
+            gQ[slot * 256 + k] = q;
+            const pf2 M = pf2{mv.x, mv.y}, Mi = pf2{mv.y, -mv.x};     // M and -i M
+            static_for<0, CAP / 16>([&](auto gi) {
+                constexpr int g = decltype(gi)::value;
+                if (16 * g <= max_lag) {                              // lags past max_lag in the last batch: never read
+                    pf2 r[16];
+                    static_for<0, 16>([&](auto ui) {
+                        constexpr int u = decltype(ui)::value, d = 16 * g + u;
+                        if constexpr (d == 0) {
+                            r[u] = pf2{rv.x, rv.y};
+                        } else {
+                            int sl = slot - d;
+                            sl += sl < 0 ? CAP : 0;
+                            const float2 x = gR[sl * 256 + k];        // zeros while t - d < 0
+                            r[u] = pf2{x.x, x.y};
+                        }
+                    });
+                    static_for<0, 16>([&](auto ui) {
+                        constexpr int u = decltype(ui)::value, d = 16 * g + u;
+                        acc[d] = acc[d] * lam;
+                        cmac_conj(acc[d], M, Mi, r[u]);
+                    });
+                }
+            });
+
+            if (ph == period - 1) {
+                ph = 0;
+                static_for<0, CAP / 16>([&](auto gi) {
+                    constexpr int g = decltype(gi)::value;
+                    if (16 * g <= max_lag) {
+                        float pw[16];
+                        static_for<0, 16>([&](auto ui) {
+                            constexpr int u = decltype(ui)::value, d = 16 * g + u;
+                            if constexpr (d == 0) {
+                                pw[u] = q;
+                            } else {
+                                int sl = slot - d;
+                                sl += sl < 0 ? CAP : 0;
+                                pw[u] = gQ[sl * 256 + k];
+                            }
+                        });
+                        static_for<0, 16>([&](auto ui) {
+                            constexpr int u = decltype(ui)::value, d = 16 * g + u;
+                            float sv = 0.f;
+                            if (k >= 1) sv = fmaf(acc[d].x, acc[d].x, acc[d].y * acc[d].y) / (pw[u] + 1e-6f);
+#pragma unroll
+                            for (int o = 32; o > 0; o >>= 1) sv += __shfl_xor(sv, o);
+                            if (lane == 0) sRed[4 * d + wave] = sv;
+                        });
+                    }
+                });
+                __syncthreads();
+                if (tid <= max_lag) {
+                    sLast = (sRed[4 * tid] + sRed[4 * tid + 1]) + (sRed[4 * tid + 2] + sRed[4 * tid + 3]);
+                    sCurve[tid] = sLast;
+                }
+                __syncthreads();
+                float bv = lane <= max_lag ? sCurve[lane] : -1.f;     // S >= 0
+                int best = lane;
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) {
+                    const float ov = __shfl_xor(bv, o);
+                    const int oi = __shfl_xor(best, o);
+                    const bool take = ov > bv || (ov == bv && oi < best);
+                    bv = take ? ov : bv;
+                    best = take ? oi : best;
+                }
+                if (best != target && bv >= p.ratio * sCurve[target]) {
+                    if (best == cand) {
+                        ++run;
+                    } else {
+                        cand = best;
+                        run = 1;
+                    }
+                    if (run >= p.hold) {
+                        target = best;
+                        run = 0;
+                    }
+                } else {
+                    run = 0;
+                }
+            } else {
+                ++ph;
+            }
+            p.ref_out[b * p.ld_out + (int64_t)j * kHop + k] = ao;
+            slot = slot + 1 == CAP ? 0 : slot + 1;
+        }
+        __syncthreads();                                              // rows consumed
+    }
+
+    static_for<0, CAP / 16>([&](auto gi) {
+        constexpr int g = decltype(gi)::value;
+        if (16 * g <= max_lag) {
+#pragma unroll
+            for (int u = 0; u < 16; ++u) gC[(16 * g + u) * 256 + k] = make_float2(acc[16 * g + u].x, acc[16 * g + u].y);
+        }
+    });
+    // the packet's last hop of both signals, and its last 64 far-end hops
+    gPrev[k] = microw[(int64_t)(cnt - 1) * kHop + k];
+    gPrev[256 + k] = refrow[(int64_t)(cnt - 1) * kHop + k];
+    for (int j = cnt > 64 ? cnt - 64 : 0; j < cnt; ++j) gSamp[((t0 + j) & 63) * 256 + k] = refrow[(int64_t)j * kHop + k];
+    if (tid < 64) gCurve[tid] = sLast;
+    if (p.curve && tid <= max_lag) p.curve[b * (max_lag + 1) + tid] = sLast;
+    if (tid == 0) {
+        gHdr[0] = t0 + cnt;
+        gHdr[1] = target;
+        gHdr[2] = cand;
+        gHdr[3] = run;
+        if (p.delay) p.delay[b] = target;
+    }
+}
+
 template <int CAP, int CHUNK>
 static hipError_t launch_delay_cap(const DelayArgs& a, int nb, hipStream_t st) {
     constexpr size_t lds = DelayCfg<CAP, CHUNK>::kBytes;
@@ -228,6 +484,24 @@ hipError_t launch_delay_estimate(const DelayArgs& a, int nb, hipStream_t st) {
     if (a.max_lag < 32) return launch_delay_cap<32, 8>(a, nb, st);
     if (a.max_lag < 48) return launch_delay_cap<48, 8>(a, nb, st);
     return launch_delay_cap<64, 4>(a, nb, st);
+}
+
+template <int CAP>
+static hipError_t launch_track_cap(const TrackArgs& a, int B, hipStream_t st) {
+    if (a.state_stride != delay_track_state_floats(CAP)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((delay_track_kernel<CAP>), dim3(B), dim3(256), TrackCfg<CAP>::kBytes, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_delay_track(const TrackArgs& a, int B, hipStream_t st) {
+    if (B <= 0) return hipSuccess;
+    if (a.max_lag < 0 || a.max_lag > kDelayMaxLag || a.max_hops < 1 || a.period < 1) return hipErrorInvalidValue;
+    switch (delay_track_cap(a.max_lag)) {
+        case 16: return launch_track_cap<16>(a, B, st);
+        case 32: return launch_track_cap<32>(a, B, st);
+        case 48: return launch_track_cap<48>(a, B, st);
+        default: return launch_track_cap<64>(a, B, st);
+    }
 }
 
 hipError_t launch_delay_apply(const ShiftArgs& a, int nb, int64_t nmax, hipStream_t st) {

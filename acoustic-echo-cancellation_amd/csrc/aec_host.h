@@ -297,6 +297,42 @@ inline Check check_delay_args(bool estimate, const void* in0, const void* in1, c
     return {};
 }
 
+// The streaming delay tracker (aec_delay_track_*; kernel and state layout in aec_delay.h).
+// Lag capacity 16 / 32 / 48 / 64 as the batch estimator picks it, and the floats of one stream's
+// state at that capacity: C and the R ring (512 each per lag), the q ring (256 per lag), 64 far-end
+// hops, the previous mic / ref hop, the latest curve and the header (a multiple of 4: rows stay
+// 16-byte aligned).  98888 floats = 386 KiB at 64 lags.
+inline int delay_track_cap(int32_t max_lag) { return max_lag < 16 ? 16 : max_lag < 32 ? 32 : max_lag < 48 ? 48 : 64; }
+inline int64_t delay_track_state_floats(int cap) { return (int64_t)1280 * cap + 64 * 256 + 2 * 256 + 64 + 8; }
+
+// aec_delay_track_open's parameters (B and aec_delay_track_config, field by field)
+inline Check check_delay_track_open(int32_t B, int32_t max_lag, int32_t period, int32_t hold, int32_t lead,
+                                    float forget, float ratio) {
+    if (B < 1) return {AEC_ERR_INVALID_ARG, "B must be >= 1"};
+    if (max_lag < 0 || max_lag > 63) return {AEC_ERR_INVALID_ARG, "max_lag out of [0, 63]"};
+    if (!(forget > 0.f && forget <= 1.f)) return {AEC_ERR_INVALID_ARG, "forget out of (0, 1]"};
+    if (period < 1) return {AEC_ERR_INVALID_ARG, "period must be >= 1"};
+    if (hold < 1) return {AEC_ERR_INVALID_ARG, "hold must be >= 1"};
+    if (!(ratio >= 1.f) || std::isinf(ratio)) return {AEC_ERR_INVALID_ARG, "ratio must be a finite number >= 1"};
+    if (lead < 0) return {AEC_ERR_INVALID_ARG, "lead must be >= 0"};
+    return {};
+}
+
+// aec_delay_track_push's packet: `open` says whether the handle has a tracker.  The shape rules are
+// aec_stream_push's (every row holds max_hops hops; the counts are device data the kernel clamps);
+// the aligned hops cannot be written over the reference they are copied from.  The kernel addresses
+// a row through 32-bit byte offsets, hence the limit on max_hops (9 hours at 16 kHz in one packet).
+inline Check check_delay_track(bool open, const void* mic, const void* ref, const void* ref_out, int32_t max_hops,
+                               int64_t ld_in, int64_t ld_out) {
+    if (!open) return {AEC_ERR_INVALID_ARG, "aec_delay_track_open first"};
+    if (!mic || !ref || !ref_out) return {AEC_ERR_INVALID_ARG, "null mic / ref / ref_out"};
+    const Check c = check_stream_push(max_hops, ld_in, ld_out);
+    if (c.status != AEC_OK) return c;
+    if ((int64_t)256 * max_hops > kDelayMaxLen) return {AEC_ERR_UNSUPPORTED, "packet longer than 2^29 - 4096 samples"};
+    if (ref_out == ref) return {AEC_ERR_INVALID_ARG, "ref_out must not be ref (the alignment cannot run in place)"};
+    return {};
+}
+
 // dst[B][4] = (mic, ref, near, 0) lengths as the kernels read them (normaliser
 // + zero padding); a signal that is not given takes mic's length
 inline void fill_slen(int32_t* dst, const int64_t* lengths3, int32_t B, int nsig) {

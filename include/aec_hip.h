@@ -243,6 +243,61 @@ aec_status aec_delay_estimate(aec_handle* h, const float* mic, const float* ref,
 aec_status aec_delay_apply(aec_handle* h, const float* ref, const int64_t* lengths, int32_t B, int64_t ld,
                            const int32_t* shift, float* out, int64_t ld_out, void* stream);
 
+/* The far-end delay while streaming (no reference counterpart): the
+ * streaming counterpart of aec_delay_estimate / aec_delay_apply, with
+ * aec_stream_push's contract.  Its state lives on the device, a call advances
+ * every stream by a packet of hops in one launch, and it emits the aligned
+ * reference hops that aec_stream_step / aec_stream_push then consume unchanged:
+ *   aec_delay_track_push(h, mic, ref, ld, aligned, ld, hops, K, delay, NULL, st);
+ *   aec_stream_push(h, mic, aligned, ld, out, ld, hops, K, st);
+ * Frames as in aec_stream_step (frame t = the Hann-windowed hops t-1 and t, hop
+ * -1 zeros, no normaliser), bins k = 1..255, M[t] / R[t] the mic / ref spectra,
+ * R[t] = 0 for t < 0.  Per stream and hop t = 0, 1, .. in this order:
+ *   1. ref_out hop t = ref hop t - s, s = max(target - lead, 0), zeros when
+ *      t - s < 0; the target is the one in force before step 4 of this hop, so a
+ *      decision made at hop t acts from hop t + 1 on
+ *   2. q[t] = forget q[t-1] + |R[t]|^2 per bin (q[-1] = 0); P_k[d] = q_k[t-d],
+ *      0 when t - d < 0
+ *   3. C_k[d] = forget C_k[d] + M_k[t] conj(R_k[t-d])        d = 0..max_lag
+ *   4. when (t + 1) % period == 0:
+ *        S[d] = sum_k |C_k[d]|^2 / (P_k[d] + 1e-6),  best = its smallest maximiser;
+ *        if best != target and S[best] >= ratio S[target]: run = run + 1 when
+ *        best == cand, else cand = best and run = 1; when run >= hold,
+ *        target = best and run = 0.  Otherwise run = 0.
+ * Start / reset: C = q = 0, target = cand = run = 0, t = 0, no samples seen.
+ *   aec_delay_track_open(h, B, cfg)   B trackers with cfg's parameters: max_lag
+ *        0..63, forget in (0, 1], period, hold >= 1, ratio >= 1, lead >= 0.
+ *        Independent of aec_stream_open, of weights, ERB matrix, canceller and
+ *        look-ahead.  Opening again replaces the state; aec_destroy frees it
+ *        (up to 386 KiB per stream: 98888 floats at 64 lags).
+ *   aec_delay_track_reset(h, b, st)   stream b (-1: every stream) back to the start
+ *   aec_delay_track_push(...)
+ *        mic, ref, ld_in, hops, max_hops: exactly as in aec_stream_push (hops a
+ *             DEVICE [B] int32 or NULL, each count clamped to [0, max_hops] by
+ *             the kernel); hand the same hops to aec_stream_push next
+ *        ref_out: device [B, ld_out]; row b receives 256 hops[b] aligned
+ *             samples, the rest of the row is not written; not ref
+ *        delay:   device [B] int32 receives the target after the packet, or NULL
+ *        curve:   device [B, max_lag + 1] receives S of the stream's latest
+ *             evaluation (zeros before the first), or NULL
+ *        A stream with 0 hops changes no byte of its state, of its ref_out row,
+ *        of delay[b] or of its curve row.  Asynchronous: never synchronises.
+ * A stream's results depend on its own samples and the open parameters alone:
+ * not on B, its row, the strides, or how its hops are cut into packets (bit for
+ * bit).  AEC_ERR_INVALID_ARG (text in aec_last_error): a parameter outside its
+ * range or B < 1 (open); no open tracker, stream index out of range (reset);
+ * no open tracker, null mic / ref / ref_out, max_hops < 1, ld_in or ld_out below
+ * 256 max_hops, ref_out == ref (push). */
+typedef struct {
+    int32_t max_lag, period, hold, lead;
+    float forget, ratio;
+} aec_delay_track_config;
+aec_status aec_delay_track_open(aec_handle* h, int32_t B, const aec_delay_track_config* cfg);
+aec_status aec_delay_track_reset(aec_handle* h, int32_t b, void* stream);
+aec_status aec_delay_track_push(aec_handle* h, const float* mic, const float* ref, int64_t ld_in, float* ref_out,
+                                int64_t ld_out, const int32_t* hops, int32_t max_hops, int32_t* delay, float* curve,
+                                void* stream);
+
 /* Debug / parity: copy an intermediate of the LAST aec_process call into the
  * device buffer dst ([B, T_max, 32] float32, frames beyond a stream's T left
  * unspecified).  Requires aec_set_debug(h, 1) before that call.
