@@ -46,13 +46,15 @@ def _rms(x):
     return float(np.sqrt(np.mean(np.square(x)) + 1e-30))
 
 
-def scene(n, seed, double_talk=True, return_echo=False):
-    """Return float32 (mic, ref, near[, echo]) of length n."""
+def scene(n, seed, double_talk=True, return_echo=False, rir_taps=1024, t60=0.25):
+    """Return float32 (mic, ref, near[, echo]) of length n.  rir_taps / t60: the room
+    response's length and decay (rir); the defaults are the 64 ms room above, a long
+    tail is e.g. rir_taps=8192, t60=0.8."""
     from scipy.signal import fftconvolve
     rng = np.random.default_rng(seed)
     ref = _ar1(rng, n) * _envelope(rng, n)
     ref *= 0.1 / _rms(ref)
-    h = rir(rng)
+    h = rir(rng, taps=rir_taps, t60=t60)
     echo = fftconvolve(ref, h)[:n]
     echo *= (_rms(ref) * 10 ** (-6 / 20)) / _rms(echo)
     if double_talk:

@@ -29,6 +29,8 @@ Extra flags (all optional):
 - `--nlms` puts the FD-NLMS stage in front of the post-filter;
 - `--kalman` puts the frequency-domain Kalman canceller there instead
   (`configs.kalman_conf`; the two flags exclude each other);
+- `--taps N` sets the canceller's taps per bin (1..16 frames of far-end
+  history, 16 ms each; default: the configuration's 4) for `--nlms` / `--kalman`;
 - `--align MAX_LAG` estimates each utterance's far-end bulk delay over lags of
   0 .. MAX_LAG frames and feeds the canceller the reference delayed by it
   (`aec_amd.delay`; off by default);
@@ -82,6 +84,8 @@ def build_parser():
     lin.add_argument('--nlms', action='store_true', help='FD-NLMS linear AEC in front of the post-filter')
     lin.add_argument('--kalman', action='store_true',
                      help='frequency-domain Kalman linear AEC in front of the post-filter')
+    p.add_argument('--taps', type=int, default=None, choices=range(1, 17), metavar='N',
+                   help='taps per bin of the --nlms / --kalman canceller, 1..16 (default: the configuration\'s 4)')
     p.add_argument('--align', type=int, default=None, metavar='MAX_LAG',
                    help='estimate the far-end bulk delay per utterance (lags 0..MAX_LAG frames, at most 63) and '
                         'feed the aligned reference; off when not given')
@@ -126,6 +130,8 @@ class Tester(object):
         local = self.args.device if self.args.device is not None else shard.local_rank()
         device = torch.device('cuda', local)
         lin = kalman_conf if getattr(self.args, 'kalman', False) else (nlms_conf if self.args.nlms else None)
+        if lin is not None and getattr(self.args, 'taps', None) is not None:
+            lin = dict(lin, taps=self.args.taps)
         net = Little_net(speech_conf, erb_conf['total_erb_bands'], nlms=lin)
         logger.info('backbone summary:\n{}'.format(net))
         param_count = sum(int(np.prod(p.shape)) for p in net.parameters())

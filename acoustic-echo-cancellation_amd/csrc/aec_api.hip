@@ -282,7 +282,7 @@ aec_status aec_create(const aec_config* cfg, const float* weights, size_t n_weig
     *out = nullptr;
     if (!cfg) return AEC_ERR_INVALID_ARG;
     if (cfg->win_size != 512 || cfg->hop_size != 256 || cfg->erb_bands != 32) return AEC_ERR_UNSUPPORTED;
-    if (cfg->nlms_taps < 0 || cfg->nlms_taps > 8) return AEC_ERR_UNSUPPORTED;
+    if (cfg->nlms_taps < 0 || cfg->nlms_taps > kMaxTaps) return AEC_ERR_UNSUPPORTED;     // 0..16 taps
     if (cfg->nlms_taps > 0 && !(cfg->nlms_mu >= 0.f && cfg->nlms_mu < 2.f && cfg->nlms_beta >= 0.f &&
                                 cfg->nlms_beta < 1.f && cfg->nlms_delta > 0.f && std::isfinite(cfg->nlms_delta)))
         return AEC_ERR_INVALID_ARG;
@@ -602,7 +602,12 @@ static aec_status process_impl(aec_handle* h, uint64_t token, const float* mic, 
         mark(h, st);
         HIP_TRY(h, launch_analysis(a, st));
         if (p.split && !p.pipe) {      // few streams: recursion per stream, then mic_erb frame-parallel
-            if (h->kalman)
+            if (h->cfg.nlms_taps > kK2nMaxTaps)      // 9..16 taps: two lanes per bin (aec_longtail.hip)
+                HIP_TRY(h, launch_longtail_recursion(h->d_rows, h->d_spec, h->d_len, Tmax, h->cfg.nlms_taps, h->kalman,
+                                                     h->kalman ? h->kal_a : h->cfg.nlms_mu, h->cfg.nlms_beta,
+                                                     h->cfg.nlms_delta, h->kal_p0, 0, B,
+                                                     h->d_rows + (size_t)B * Tmax * 512, st));
+            else if (h->kalman)
                 HIP_TRY(h, launch_kalman_recursion(h->d_rows, h->d_spec, h->d_len, Tmax, h->cfg.nlms_taps, h->kal_a,
                                                    h->cfg.nlms_beta, h->cfg.nlms_delta, h->kal_p0, 0, B,
                                                    h->d_rows + (size_t)B * Tmax * 512, st));

@@ -19,6 +19,8 @@ namespace aec {
 constexpr int kFPB = 16;            // frames per analysis / synthesis block (16 groups x 16 lanes)
 constexpr int kHopsOut = kFPB - 1;  // output hops per synthesis block
 constexpr int kPipeTaps = 4;        // the one tap count the small-batch pipeline is instantiated for
+constexpr int kK2nMaxTaps = 8;      // most taps K2n (and the per-lane recursion kernel) is instantiated for
+constexpr int kMaxTaps = 16;        // most taps of the linear stage (256 ms of far-end history)
 
 inline int64_t num_frames(int64_t n) { return n / 256 + 1; }
 // Floats of one stream's state (aec_stream_*; layout in aec_launch.h): 1024, then one row of 256
@@ -406,7 +408,9 @@ struct Plan {
 };
 
 inline Plan plan_call(const PlanIn& in) {
-    const bool small = in.B <= in.small_b && in.nlms_mode == 0;
+    // 9..16 taps: the long-tail recursion (aec_longtail.hip) exists for the split plan only, so
+    // these calls take it at every B and never K2n or the pipeline
+    const bool small = (in.B <= in.small_b && in.nlms_mode == 0) || in.nlms_taps > kK2nMaxTaps;
     const bool fused = in.fused && in.gru_mode == 0;
     const bool half = 2 * (int64_t)in.B <= (int64_t)in.num_cus;
     Plan p;

@@ -171,6 +171,11 @@ hipError_t launch_nlms_recursion(const float2* rows, float2* spec, const int64_t
 hipError_t launch_kalman_recursion(const float2* rows, float2* spec, const int64_t* lens, int64_t Tmax, int taps,
                                    float a, float beta, float delta, float p0, int b0, int nb, float2* dummy_rows,
                                    hipStream_t st);
+// 9..16 taps (aec_longtail.hip): the recursion of the split path; the Kalman canceller with two
+// lanes per bin, each running one of the two partial chains of KalmanBin::step (mu carries a)
+hipError_t launch_longtail_recursion(const float2* rows, float2* spec, const int64_t* lens, int64_t Tmax, int taps,
+                                     int kalman, float mu, float beta, float delta, float p0, int b0, int nb,
+                                     float2* dummy_rows, hipStream_t st);
 hipError_t launch_mic_erb(const float2* spec, float* feats, const int64_t* lens, int64_t Tmax, const float* sched,
                           int sched_len, const WorkItem* items, int64_t nitems, hipStream_t st);
 hipError_t launch_gru(const GruArgs& a, int B, hipStream_t st);
@@ -179,6 +184,9 @@ hipError_t launch_stream_step(const StreamStepArgs& a, int B, int taps, hipStrea
 hipError_t launch_stream_push(const StreamPushArgs& a, int B, int taps, hipStream_t st);
 hipError_t launch_stream_cov_fill(float* state, int64_t stride, int first, int count, int taps, float p0,
                                   hipStream_t st);
+// 9..16 taps (aec_stream_long.hip): the same kernel templates; launch_stream_step / _push forward here
+hipError_t launch_stream_step_long(const StreamStepArgs& a, int B, int taps, hipStream_t st);
+hipError_t launch_stream_push_long(const StreamPushArgs& a, int B, int taps, hipStream_t st);
 // K3+K4 fused (aec_gru_synth.hip): GRU + head + synthesis of the NLMS error spectrum, one stream per
 // block or two (Plan::gru_one, aec_host.h)
 hipError_t launch_gru_synth(const GruArgs& g, const SynthArgs& y, int B, bool one_per_block, hipStream_t st);

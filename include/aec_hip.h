@@ -56,7 +56,7 @@ typedef struct {
     int32_t win_size;    /* 512  (speech_conf['win_size'])  — only 512 supported  */
     int32_t hop_size;    /* 256  (speech_conf['hop_size'])  — only 256 supported  */
     int32_t erb_bands;   /* 32   (erb_conf['total_erb_bands']); GRU hidden = bands */
-    int32_t nlms_taps;   /* 0 = bypass; 1..8 taps per bin (frames of far-end history) */
+    int32_t nlms_taps;   /* 0 = bypass; 1..16 taps per bin (frames of far-end history) */
     float   nlms_mu;     /* step size, [0, 2); 0 leaves the mic spectrum unchanged    */
     float   nlms_beta;   /* far-end power smoothing, [0, 1)                           */
     float   nlms_delta;  /* regulariser, > 0                                          */
@@ -200,7 +200,7 @@ aec_status aec_stream_step(aec_handle* h, const float* mic, const float* ref, in
  *   max_hops: >= 1, with ld_in, ld_out >= 256 max_hops; no other limit
  *             (max_hops == 1 with hops == NULL launches aec_stream_step's kernel)
  * aec_stream_step, aec_stream_push and aec_stream_reset mix freely on one
- * handle (one state layout at call boundaries), for nlms_taps 0..8 and both
+ * handle (one state layout at call boundaries), for nlms_taps 0..16 and both
  * cancellers.  AEC_ERR_INVALID_ARG (text in aec_last_error): no open stream
  * state, weights / ERB not set, null mic / ref / out, max_hops < 1, ld_in or
  * ld_out below 256 max_hops. */
@@ -208,7 +208,7 @@ aec_status aec_stream_push(aec_handle* h, const float* mic, const float* ref, in
                            float* out, int64_t ld_out, const int32_t* hops, int32_t max_hops, void* stream);
 
 /* Far-end bulk delay (no reference counterpart).  The cancellers
- * see nlms_taps <= 8 frames (128 ms) of far-end history; play-out and capture
+ * see nlms_taps <= 16 frames (256 ms) of far-end history; play-out and capture
  * buffering put 50 .. 500 ms between ref and its echo in mic.  aec_delay_estimate
  * finds that offset in whole frames, aec_delay_apply delays ref by it, and the
  * canceller then runs unchanged on the aligned reference.
