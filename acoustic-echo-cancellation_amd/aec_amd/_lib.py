@@ -36,7 +36,8 @@ EXPORTS = ('aec_weights_count', 'aec_create', 'aec_set_weights', 'aec_set_erb', 
 
 
 # every symbol include/aec_crn.h declares
-CRN_EXPORTS = ('aec_crn_param_count', 'aec_crn_create', 'aec_crn_set_params', 'aec_crn_process', 'aec_crn_stft',
+CRN_EXPORTS = ('aec_crn_param_count', 'aec_crn_create', 'aec_crn_set_params', 'aec_crn_set_canceller',
+               'aec_crn_process', 'aec_crn_stft',
                'aec_crn_error_spec',
                'aec_crn_stream_open', 'aec_crn_stream_reset', 'aec_crn_stream_step',
                'aec_crn_stream_set_graph', 'aec_crn_stream_stats', 'aec_crn_profile_enable', 'aec_crn_profile_read', 'aec_crn_last_error', 'aec_crn_destroy')
@@ -169,6 +170,8 @@ def load():
     lib.aec_crn_create.restype = ctypes.c_int
     lib.aec_crn_set_params.argtypes = [P, P, ctypes.c_size_t]
     lib.aec_crn_set_params.restype = ctypes.c_int
+    lib.aec_crn_set_canceller.argtypes = [P, ctypes.c_int32, ctypes.c_float, ctypes.c_float]
+    lib.aec_crn_set_canceller.restype = ctypes.c_int
     lib.aec_crn_process.argtypes = [P, P, P, P, ctypes.c_int32, ctypes.c_int64, P, ctypes.c_int64, P, P, P]
     lib.aec_crn_process.restype = ctypes.c_int
     lib.aec_crn_stft.argtypes = [P, P, P, ctypes.c_int32, ctypes.c_int64, P, P]
@@ -409,7 +412,8 @@ def crn_config(version, conf, dtype, nlms=None):
     c.masking_mode = ord(conf.get('masking_mode', 'C')[0]) if version == 2 else ord('C')
     c.dtype = {'f32': 0, 'float32': 0, 'bf16': 1, 'bfloat16': 1, 'fp8': 2, 'mxfp8': 2}[dtype]
     if nlms and nlms.get('kind', 'nlms') != 'nlms':
-        raise NotImplementedError(f"the CRN front end runs the FD-NLMS only, not kind={nlms['kind']!r}")
+        raise NotImplementedError(f"the CRN config describes the FD-NLMS only, not kind={nlms['kind']!r}: "
+                                  "select the Kalman canceller with set_canceller('kalman', a=..., p0=...)")
     if nlms:
         c.nlms_taps = int(nlms.get('taps', 4))
         c.nlms_mu = float(nlms.get('mu', 0.3))
@@ -439,6 +443,12 @@ class CrnHandle:
         import numpy as np
         blob = np.ascontiguousarray(blob, dtype=np.float32)
         check(self.lib.aec_crn_set_params(self.h, blob.ctypes.data, blob.size), self.h, 'aec_crn_set_params', True)
+
+    def set_canceller(self, kind, a=1.0, p0=0.0):
+        """kind: 'nlms' / 0 or 'kalman' / 1 (aec_crn_set_canceller)."""
+        kind = {'nlms': 0, 'kalman': 1}.get(kind, kind)
+        check(self.lib.aec_crn_set_canceller(self.h, int(kind), float(a), float(p0)), self.h, 'aec_crn_set_canceller',
+              True)
 
     def process(self, mic_ptr, far_ptr, lengths, B, ld, out_ptr, ld_out, spec_ptr, mask_ptr, stream):
         import numpy as np

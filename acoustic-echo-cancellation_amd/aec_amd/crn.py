@@ -115,8 +115,9 @@ class _DCCRNBase(nn.Module):
         self.dtype_name = dtype
         self.nlms = dict(nlms) if nlms else None   # build-defined FD-NLMS front end (include/aec_crn.h)
         if self.nlms and self.nlms.get('kind', 'nlms') != 'nlms':
-            raise NotImplementedError(f"the CRN front end runs the FD-NLMS only, not kind={self.nlms['kind']!r}: "
-                                      "the Kalman canceller is Little_net's (configs.kalman_conf)")
+            raise NotImplementedError(f"nlms= describes the FD-NLMS only, not kind={self.nlms['kind']!r}: "
+                                      "select the Kalman canceller with set_canceller('kalman', a=..., p0=...)")
+        self._canceller = None                     # set_canceller's (kind, a, p0); None: the library's default (NLMS)
         self._handles = {}
         self._p_key = {}
         self._last_shape = {}                      # device index -> (B, Tmax) of the last forward
@@ -158,6 +159,8 @@ class _DCCRNBase(nn.Module):
         h = self._handles.get(idx)
         if h is None:
             h = _lib.CrnHandle(self.VERSION, self.config, self.dtype_name, idx, self.nlms)
+            if self._canceller is not None:
+                h.set_canceller(*self._canceller)
             self._handles[idx] = h
         sd = self.state_dict(keep_vars=True)
         key = tuple((sd[n].data_ptr(), sd[n]._version) for n in self.param_names())
@@ -165,6 +168,21 @@ class _DCCRNBase(nn.Module):
             h.set_params(self.params_blob())
             self._p_key[idx] = key
         return h
+
+    def set_canceller(self, kind, a=1.0, p0=0.0):
+        """The linear stage's adaptive filter (aec_crn_set_canceller): 'nlms', the
+        FD-NLMS of ``nlms=`` (the default), or 'kalman', the frequency-domain
+        Kalman filter with transition factor ``a`` in (0, 1] and initial tap
+        covariance ``p0`` >= 0 (``configs.kalman_conf``: a=0.999, p0=1.0); taps,
+        beta and delta stay those of ``nlms=``, mu is unused.  Applies at once
+        to the handles that exist and to every handle created later.  Raises
+        RuntimeError with the library's text for a bad argument or while a
+        stream is open (the stream state's layout depends on the kind)."""
+        if not self.nlms:
+            raise RuntimeError('set_canceller needs a network built with nlms=... (there is no linear stage)')
+        for h in self._handles.values():
+            h.set_canceller(kind, a, p0)
+        self._canceller = (kind, float(a), float(p0))
 
     # ---- forward --------------------------------------------------------------
     def _check(self, *xs):
@@ -196,7 +214,7 @@ class _DCCRNBase(nn.Module):
         return torch.cat([spec[..., 0], spec[..., 1]], dim=2).transpose(1, 2)
 
     def error_spectra(self, device):
-        """NLMS networks: the FD-NLMS error spectrum E of the last forward on
+        """NLMS networks: the canceller's (FD-NLMS or Kalman) error spectrum E of the last forward on
         ``device`` (the spectrum the mask was applied to) -> [B, 514, T]."""
         if not self.nlms:
             raise RuntimeError('error_spectra needs a network built with nlms=...')

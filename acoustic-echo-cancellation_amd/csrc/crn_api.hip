@@ -72,6 +72,9 @@ struct aec_crn_handle : Net<Packed> {              // cfg, the derived sizes and
     std::vector<int64_t> proc_lens;                //   and its lengths
     std::vector<void*> allocs;
     StreamState* ss = nullptr;                     // aec_crn_stream_* state
+    // the linear stage's adaptive filter (aec_crn_set_canceller): 0 FD-NLMS, 1 frequency-domain Kalman
+    int kalman = 0;
+    float kal_a = 1.f, kal_p0 = 0.f;
     // persistent LSTM recurrence (crn_persist.hip; AEC_CRN_PERSIST=0: one launch per frame)
     int persist = 1;
     int num_cus = 0;
@@ -641,9 +644,13 @@ static aec_status run(aec_crn_handle* h, const float* mic, const float* far, int
     crn::FrontArgs fa{mic, far, ld, h->d_len, Tmax, h->d_tab, h->x0, nullptr};
     if (c.nlms_taps > 0) fa.rows = h->nrows;
     CRN_TRY(h, crn::launch_front<T>(fa, B, st));
-    if (c.nlms_taps > 0) {   // FD-NLMS: rows -> E rows (one block per stream) -> X0
-        CRN_TRY(h, aec::launch_nlms_recursion(h->nrows, h->espec, h->d_len, Tmax, c.nlms_taps, c.nlms_mu, c.nlms_beta,
-                                              c.nlms_delta, 0, B, h->ndummy, st));
+    if (c.nlms_taps > 0) {   // canceller: rows -> E rows (one block per stream) -> X0
+        if (h->kalman)
+            CRN_TRY(h, aec::launch_kalman_recursion(h->nrows, h->espec, h->d_len, Tmax, c.nlms_taps, h->kal_a, c.nlms_beta,
+                                                    c.nlms_delta, h->kal_p0, 0, B, h->ndummy, st));
+        else
+            CRN_TRY(h, aec::launch_nlms_recursion(h->nrows, h->espec, h->d_len, Tmax, c.nlms_taps, c.nlms_mu, c.nlms_beta,
+                                                  c.nlms_delta, 0, B, h->ndummy, st));
         crn::RowsX0Args xa{h->nrows, h->espec, h->d_len, Tmax, h->x0, B};
         CRN_TRY(h, crn::launch_rows_x0<T>(xa, st));
     }
@@ -753,7 +760,7 @@ struct StreamState {
                                          //   copies each call's hops in, for the next call and the back kernel
     float* tail = nullptr;               // [B][256] overlap-add tail
     float2* nrows = nullptr;             // NLMS: packed rows [B][2][256]
-    float2* nstate = nullptr;            //       recursion state [B][2*taps][256]
+    float2* nstate = nullptr;            //       recursion state [B][rows][256] (crn_canceller_state_rows)
     float2* espec = nullptr;             //       E rows [B][256]
     // one hipGraph per ring parity; the caller's hop / output buffers change per call, so the
     // front and back kernel nodes get this call's pointers by hipGraphExecKernelNodeSetParams
@@ -892,6 +899,16 @@ static aec_status run_lstm_mx_step(aec_crn_handle* h, StreamState& ss, const Buf
     return AEC_OK;
 }
 
+// A fresh Kalman state is zero except the covariance rows P = p0: streams first .. first + count - 1.
+// The canceller block has the Little_net stream state's row order, so its fill kernel serves: it
+// addresses the block at state + stream * stride + kStNlms, hence the base pointer kStNlms floats
+// before this state (only rows inside the state are touched).
+static hipError_t stream_cov_fill(aec_crn_handle* h, int first, int count, hipStream_t st) {
+    const CancellerRows cr = crn_canceller_state_rows(h->cfg.nlms_taps, true);
+    return aec::launch_stream_cov_fill(reinterpret_cast<float*>(h->ss->nstate) - aec::kStNlms, cr.floats(), first, count,
+                                       h->cfg.nlms_taps, h->kal_p0, st);
+}
+
 // the fused front's level table (stream_open checked the shapes: stream_enc_levels)
 static crn::StreamEncArgs stream_enc_args(aec_crn_handle* h, int B) {
     StreamState& ss = *h->ss;
@@ -902,9 +919,11 @@ static crn::StreamEncArgs stream_enc_args(aec_crn_handle* h, int B) {
     if (h->cfg.nlms_taps > 0) {
         ea.state = ss.nstate;
         ea.espec = ss.espec;
-        ea.mu = h->cfg.nlms_mu;
+        ea.mu = h->kalman ? h->kal_a : h->cfg.nlms_mu;
         ea.beta = h->cfg.nlms_beta;
         ea.delta = h->cfg.nlms_delta;
+        ea.p0 = h->kal_p0;
+        ea.kalman = h->kalman;
     }
     ea.nlev = ss.enc_nlev;
     if (ss.enc_mx) {
@@ -1009,6 +1028,7 @@ static bool stream_dec_mx_ok(const aec_crn_handle* h) {
 static bool stream_enc_mx_ok(const aec_crn_handle* h) {
     if (!(AEC_MODE_KNOB("AEC_CRN_STREAM_FUSE", 31) & 16)) return false;
     if (h->L < 6 || !h->ss) return false;
+    if (h->kalman && h->cfg.nlms_taps > 0 && !crn::stream_enc_kalman_ok(h->cfg.nlms_taps, true)) return false;
     const int* ch = h->cfg.conv_channels;
     const Packed& pk = h->enc[4];
     const StreamState& ss = *h->ss;
@@ -1023,6 +1043,8 @@ static int stream_enc_levels(const aec_crn_handle* h) {
     if (h->es != 2) return 0;
     const int fuse = AEC_MODE_KNOB("AEC_CRN_STREAM_FUSE", 31);
     if (!(fuse & 1)) return 0;
+    // a Kalman fused front that is not built (it would spill): the separate launches
+    if (h->kalman && h->cfg.nlms_taps > 0 && !crn::stream_enc_kalman_ok(h->cfg.nlms_taps, false)) return 0;
     const int* ch = h->cfg.conv_channels;
     int n = 0;
     // levels 0-2 together, at net_conf's shapes (crn_stream_enc_kernel's compile-time chunk counts)
@@ -1087,7 +1109,13 @@ static aec_status stream_launches(aec_crn_handle* h, int par, const StreamIo& io
         ss.front_args[par] = fa;
         if (c.nlms_taps > 0) {
             crn::StreamNlmsArgs na{ss.nrows, ss.nstate, ss.espec, ss.x0, B, c.nlms_mu, c.nlms_beta, c.nlms_delta};
-            CRN_TRY(h, crn::launch_stream_nlms<T>(na, c.nlms_taps, st));
+            if (h->kalman) {
+                crn::StreamKalmanArgs ka{na, h->kal_p0};
+                ka.mu = h->kal_a;
+                CRN_TRY(h, crn::launch_stream_kalman<T>(ka, c.nlms_taps, st));
+            } else {
+                CRN_TRY(h, crn::launch_stream_nlms<T>(na, c.nlms_taps, st));
+            }
         }
     }
     aec_status s = run_encoder<T>(h, bf, B, st, first);
@@ -1321,6 +1349,19 @@ aec_status aec_crn_error_spec(aec_crn_handle* h, float* spec, void* stream) {
     return AEC_OK;
 }
 
+aec_status aec_crn_set_canceller(aec_crn_handle* h, int32_t kind, float a, float p0) {
+    if (!h) return AEC_ERR_INVALID_ARG;
+    bool unsupported = false;
+    const std::string why = check_canceller(h->cfg.nlms_taps, kind, a, p0, h->ss != nullptr, &unsupported);
+    if (!why.empty()) return crn_fail(h, unsupported ? AEC_ERR_UNSUPPORTED : AEC_ERR_INVALID_ARG, why);
+    if (kind == 1) {
+        h->kal_a = a;
+        h->kal_p0 = p0;
+    }
+    h->kalman = kind;
+    return AEC_OK;
+}
+
 aec_status aec_crn_stream_open(aec_crn_handle* h, int32_t B) {
     if (!h || B <= 0) return AEC_ERR_INVALID_ARG;
     if (!h->have_params) return crn_fail(h, AEC_ERR_INVALID_ARG, "parameters not set");
@@ -1412,7 +1453,9 @@ aec_status aec_crn_stream_open(aec_crn_handle* h, int32_t B) {
     CRN_TRY(h, alloc(reinterpret_cast<void**>(&ss.tail), (size_t)B * 256 * sizeof(float)));
     if (h->cfg.nlms_taps > 0) {
         CRN_TRY(h, alloc(reinterpret_cast<void**>(&ss.nrows), (size_t)B * 512 * sizeof(float2)));
-        CRN_TRY(h, alloc(reinterpret_cast<void**>(&ss.nstate), (size_t)B * 2 * h->cfg.nlms_taps * 256 * sizeof(float2)));
+        const CancellerRows cr = crn_canceller_state_rows(h->cfg.nlms_taps, h->kalman != 0);
+        CRN_TRY(h, alloc(reinterpret_cast<void**>(&ss.nstate), (size_t)B * cr.bytes()));
+        if (h->kalman) CRN_TRY(h, stream_cov_fill(h, 0, B, nullptr));
         CRN_TRY(h, alloc(reinterpret_cast<void**>(&ss.espec), (size_t)B * 256 * sizeof(float2)));
     }
     ss.enc_nlev = stream_enc_levels(h);
@@ -1487,9 +1530,15 @@ aec_status aec_crn_stream_reset(aec_crn_handle* h, int32_t b, void* stream) {
     for (int q = 0; q < 4; ++q)
         CRN_TRY(h, hipMemsetAsync(ss.hop + ((size_t)q * ss.B + b0) * 256, 0, (size_t)nb * 256 * sizeof(float), st));
     CRN_TRY(h, hipMemsetAsync(ss.tail + (size_t)b0 * 256, 0, (size_t)nb * 256 * sizeof(float), st));
-    if (ss.nstate) {   // NLMS: W, history, P = 0 (a fresh recursion)
-        const size_t srow = (size_t)2 * h->cfg.nlms_taps * 256;
+    if (ss.nstate) {   // a fresh recursion: W, history, power / psi = 0; Kalman: P = p0 again
+        const CancellerRows cr = crn_canceller_state_rows(h->cfg.nlms_taps, h->kalman != 0);
+        const size_t srow = (size_t)cr.rows * 256;
         CRN_TRY(h, hipMemsetAsync(ss.nstate + b0 * srow, 0, nb * srow * sizeof(float2), st));
+        if (h->kalman) {
+            aec::DeviceGuard dg(h->device);
+            if (dg.err != hipSuccess) return crn_fail(h, AEC_ERR_HIP, "hipSetDevice failed");
+            CRN_TRY(h, stream_cov_fill(h, b0, nb, st));
+        }
     }
     if (b < 0) ss.k = 0;
     return AEC_OK;

@@ -24,6 +24,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "aec_fft.h"
 #include "aec_frame.h"
 #include "aec_stft.h"
@@ -580,14 +582,18 @@ __global__ __launch_bounds__(256) void crn_rows_x0_kernel(RowsX0Args p) {
     x0_bin<T>(row, k, e, fr);
 }
 
-template <typename T, int TAPS>
-__global__ __launch_bounds__(256) void crn_stream_nlms_kernel(StreamNlmsArgs p) {
+// KALMAN: the canceller is aec::KalmanBin (p.mu carries its transition factor a; the state gains the
+// covariance rows and psi: crn_host.h crn_canceller_state_rows), else aec::NlmsBin
+template <typename T, int TAPS, bool KALMAN>
+__global__ __launch_bounds__(256) void crn_stream_nlms_kernel(
+    std::conditional_t<KALMAN, StreamKalmanArgs, StreamNlmsArgs> p) {
     const int b = blockIdx.x, k = threadIdx.x;
-    float2* nst = p.state + (int64_t)b * (2 * TAPS) * 256;
+    float2* nst = p.state + (int64_t)b * (KALMAN ? 3 * TAPS + 1 : 2 * TAPS) * 256;
     // restore (aec_stream.hip's layout: taps, raw far history, power); the
     // history operands are re-derived with step()'s own expressions
-    aec::NlmsBin<TAPS> nb;
-    nb.reset(k == 0);
+    std::conditional_t<KALMAN, aec::KalmanBin<TAPS>, aec::NlmsBin<TAPS>> nb;
+    if constexpr (KALMAN) nb.reset(k == 0, p.p0);
+    else nb.reset(k == 0);
     float2 rh[TAPS > 1 ? TAPS - 1 : 1];
 #pragma unroll
     for (int l = 0; l < TAPS; ++l) {
@@ -600,8 +606,14 @@ __global__ __launch_bounds__(256) void crn_stream_nlms_kernel(StreamNlmsArgs p) 
         rh[l] = r2;
         nb.hist(l, r2);
     }
-    const float2 pp = nst[(2 * TAPS - 1) * 256 + k];
-    nb.p = pp;
+    if constexpr (KALMAN) {
+#pragma unroll
+        for (int l = 0; l < TAPS; ++l) nb.pp[l] = nst[(2 * TAPS + l) * 256 + k];
+        nb.p = nst[3 * TAPS * 256 + k];
+    } else {
+        const float2 pp = nst[(2 * TAPS - 1) * 256 + k];
+        nb.p = pp;
+    }
     const float2* rows = p.rows + (int64_t)b * 512;
     const float2 r = rows[256 + k];
     const float2 e = nb.step(rows[k], r, p.mu, p.beta, p.delta);
@@ -612,7 +624,13 @@ __global__ __launch_bounds__(256) void crn_stream_nlms_kernel(StreamNlmsArgs p) 
 #pragma unroll
         for (int l = 1; l + 1 < TAPS; ++l) nst[(TAPS + l) * 256 + k] = rh[l - 1];
     }
-    nst[(2 * TAPS - 1) * 256 + k] = nb.p;
+    if constexpr (KALMAN) {
+#pragma unroll
+        for (int l = 0; l < TAPS; ++l) nst[(2 * TAPS + l) * 256 + k] = nb.pp[l];
+        nst[3 * TAPS * 256 + k] = nb.p;
+    } else {
+        nst[(2 * TAPS - 1) * 256 + k] = nb.p;
+    }
     float2* erow = p.espec + (int64_t)b * 256;
     erow[k] = e;
     // X0 bin k (k >= 1) or, on lane 0, the Nyquist bin: from this lane's own
@@ -664,7 +682,7 @@ hipError_t launch_stream_nlms(const StreamNlmsArgs& a, int taps, hipStream_t st)
     if (a.B <= 0) return hipSuccess;
     switch (taps) {
 #define CRN_NLMS_CASE(N) \
-        case N: hipLaunchKernelGGL((crn_stream_nlms_kernel<T, N>), dim3((unsigned)a.B), dim3(256), 0, st, a); break;
+        case N: hipLaunchKernelGGL((crn_stream_nlms_kernel<T, N, false>), dim3((unsigned)a.B), dim3(256), 0, st, a); break;
         CRN_NLMS_CASE(1) CRN_NLMS_CASE(2) CRN_NLMS_CASE(3) CRN_NLMS_CASE(4)
         CRN_NLMS_CASE(5) CRN_NLMS_CASE(6) CRN_NLMS_CASE(7) CRN_NLMS_CASE(8)
 #undef CRN_NLMS_CASE
@@ -674,6 +692,22 @@ hipError_t launch_stream_nlms(const StreamNlmsArgs& a, int taps, hipStream_t st)
 }
 template hipError_t launch_stream_nlms<float>(const StreamNlmsArgs&, int, hipStream_t);
 template hipError_t launch_stream_nlms<bf16_t>(const StreamNlmsArgs&, int, hipStream_t);
+
+template <typename T>
+hipError_t launch_stream_kalman(const StreamKalmanArgs& a, int taps, hipStream_t st) {
+    if (a.B <= 0) return hipSuccess;
+    switch (taps) {
+#define CRN_KALMAN_CASE(N) \
+        case N: hipLaunchKernelGGL((crn_stream_nlms_kernel<T, N, true>), dim3((unsigned)a.B), dim3(256), 0, st, a); break;
+        CRN_KALMAN_CASE(1) CRN_KALMAN_CASE(2) CRN_KALMAN_CASE(3) CRN_KALMAN_CASE(4)
+        CRN_KALMAN_CASE(5) CRN_KALMAN_CASE(6) CRN_KALMAN_CASE(7) CRN_KALMAN_CASE(8)
+#undef CRN_KALMAN_CASE
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+template hipError_t launch_stream_kalman<float>(const StreamKalmanArgs&, int, hipStream_t);
+template hipError_t launch_stream_kalman<bf16_t>(const StreamKalmanArgs&, int, hipStream_t);
 
 template <typename T>
 hipError_t launch_stream_front(const StreamFrontArgs& a, hipStream_t st) {

@@ -169,6 +169,13 @@ struct StreamNlmsArgs {
     int32_t B;
     float mu, beta, delta;
 };
+// The same step with the Kalman canceller (aec::KalmanBin; mu carries its transition factor a),
+// state [B][3*TAPS+1][256]: the NLMS rows (its power row unused), then the TAPS covariance rows
+// and psi (crn_host.h crn_canceller_state_rows).  A type of its own: the NLMS kernels keep
+// their argument block, so they compile to the code they were.
+struct StreamKalmanArgs : StreamNlmsArgs {
+    float p0 = 0.f;             // the initial covariance (KalmanBin::reset)
+};
 struct StreamBackArgs {
     const float* prev_mic;
     const float* cur_mic;
@@ -229,8 +236,18 @@ struct StreamEncArgs {
     int32_t nlev;               // 3 or 4 (level 3: 16 output bins x 128 channels, K = 320)
     StreamEncLevel lev[4];
     StreamEncMxLevel mx4;       // mx4.wq non-null (nlev == 4): level 4 as well
+    // Kalman canceller (after every NLMS field: their offsets stay put): state is
+    // [B][3 taps + 1][256] (StreamNlmsArgs), mu carries a
+    float p0 = 0.f;
+    int32_t kalman = 0;
 };
 hipError_t launch_stream_enc(const StreamEncArgs& a, int taps, hipStream_t st);
+// The Kalman instantiations (crn_stream_kalman.hip); launch_stream_enc checks the arguments and
+// forwards here when a.kalman.  stream_enc_kalman_ok: the (taps, MX4) forms that are built, i.e.
+// that compile without scratch (profiles/crn_kalman_canceller.txt); any other would take the
+// unfused launches (crn_api.hip stream_enc_levels / stream_enc_mx_ok)
+hipError_t launch_stream_enc_kalman(const StreamEncArgs& a, int taps, hipStream_t st);
+bool stream_enc_kalman_ok(int taps, bool mx4);
 
 // Batch encoder front (crn_stream.hip): encoder levels 0-3 of F frames from X0 [F][256][8]
 // (frame f's level-i map at lev[i].out + f * Fo_i * ldo + choff), the four levels' shapes as
@@ -305,6 +322,8 @@ hipError_t launch_stream_front(const StreamFrontArgs& a, hipStream_t st);
 hipError_t launch_stream_back(const StreamBackArgs& a, int mode, hipStream_t st);
 template <typename T>
 hipError_t launch_stream_nlms(const StreamNlmsArgs& a, int taps, hipStream_t st);
+template <typename T>
+hipError_t launch_stream_kalman(const StreamKalmanArgs& a, int taps, hipStream_t st);
 template <typename T>
 hipError_t launch_rows_x0(const RowsX0Args& a, hipStream_t st);
 hipError_t launch_unpack_rows(const float2* espec, const int64_t* lens, int B, int64_t Tmax, float2* spec,

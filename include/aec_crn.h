@@ -68,7 +68,9 @@ typedef struct {
      * aec_hip.h (same recursion, same parameter meaning) driven by the far
      * spectrum; E feeds the encoder's mic channels AND is the spectrum the
      * decoder's mask is applied to (out_spec / out_wav).  The far channels
-     * stay X_far.  Streaming carries the NLMS state per stream. */
+     * stay X_far.  Streaming carries the canceller state per stream.
+     * aec_crn_set_canceller (below) selects the frequency-domain Kalman filter
+     * in place of the NLMS recursion; this struct is the same for both. */
     int32_t nlms_taps;          /* 0 = off; 1..8 */
     float   nlms_mu;            /* [0, 2)  */
     float   nlms_beta;          /* [0, 1)  */
@@ -95,6 +97,32 @@ aec_status aec_crn_create(const aec_crn_config* cfg, const float* params, size_t
                           aec_crn_handle** out);
 aec_status aec_crn_set_params(aec_crn_handle* h, const float* params, size_t n_params);
 
+/* The linear stage's adaptive filter, for handles with nlms_taps > 0; the
+ * contract of aec_set_canceller (aec_hip.h):
+ *   kind 0  the FD-NLMS of the config (the default: a handle that never calls
+ *           this behaves as before; a and p0 are ignored)
+ *   kind 1  the diagonalised frequency-domain Kalman filter (process noise from
+ *           the tap energy).  Per bin k and frame t, with R_l = R[t-l] the far
+ *           spectrum l frames back (W = 0, P = p0, psi = 0 at the start):
+ *             E    = D - sum_l W[l] R_l                  (a-priori error = output)
+ *             psi  = beta psi + (1 - beta) |E|^2
+ *             S    = sum_l P[l] |R_l|^2 + psi + delta,   G_l = P[l] / S
+ *             W[l] = a (W[l] + G_l conj(R_l) E)
+ *             P[l] = a^2 (1 - G_l |R_l|^2) P[l] + (1 - a^2) |W[l]|^2
+ *           beta = nlms_beta and delta = nlms_delta of the config; nlms_mu is
+ *           ignored.  a in (0, 1] is the tap transition factor (1: a static echo
+ *           path, no process noise), p0 >= 0 and finite the initial tap
+ *           covariance (0 never adapts: E = D).  Float32 per bin, as the NLMS.
+ * Everything downstream is unchanged: E feeds the encoder's mic channels, is
+ * the spectrum the mask is applied to, and is what aec_crn_error_spec returns.
+ * All three dtypes, the batch call and the per-hop step (direct and hipGraph).
+ * The choice holds for later aec_crn_process and aec_crn_stream_open calls.
+ * AEC_ERR_INVALID_ARG: unknown kind, a or p0 out of range, or a streaming
+ * state open on the handle (its layout depends on the kind; a and p0 are
+ * kernel arguments of the captured per-hop graphs).  AEC_ERR_UNSUPPORTED:
+ * nlms_taps == 0. */
+aec_status aec_crn_set_canceller(aec_crn_handle* h, int32_t kind, float a, float p0);
+
 /* Run the CRN for B utterances.
  *   mic, far : device [B, ld] float32, row b holds lengths[b] samples
  *   lengths  : host [B] int64, each in [1, ld]; T_b = lengths[b]/256 + 1,
@@ -115,7 +143,7 @@ aec_status aec_crn_set_params(aec_crn_handle* h, const float* params, size_t n_p
 aec_status aec_crn_process(aec_crn_handle* h, const float* mic, const float* far, const int64_t* lengths, int32_t B,
                            int64_t ld, float* out, int64_t ld_out, float* spec, float* mask, void* stream);
 
-/* NLMS handles (nlms_taps > 0): the FD-NLMS error spectrum E of the last
+/* NLMS handles (nlms_taps > 0): the canceller's (FD-NLMS or Kalman) error spectrum E of the last
  * aec_crn_process call -> device [B, Tmax, 257] float2 (frames t >= T_b zero),
  * the spectrum the mask was applied to (the v1 loss's cRM reference,
  * dccrn.py:556-566, when the network is fed E). */
@@ -140,8 +168,13 @@ aec_status aec_crn_stft(aec_crn_handle* h, const float* x, const int64_t* length
  * encoder / decoder level 4 into the fused kernels only while B <= the
  * device's CU count (above that they are separate launches; the results are
  * bit-identical either way).
- *   aec_crn_stream_open(h, B)        B concurrent streams; state zeroed
- *   aec_crn_stream_reset(h, b, st)   zero stream b's state (-1: all, and the hop counter)
+ * Per stream the canceller keeps rows of 256 float2 (one per bin slot; slot 0
+ * holds the real bins 0 and 256): W[0 .. taps), the far history R[t-1 ..
+ * t-taps+1], the NLMS power (2 taps rows); the Kalman canceller adds the taps
+ * covariance rows P and one row psi (3 taps + 1 rows).  A fresh state is zero
+ * except P = p0.
+ *   aec_crn_stream_open(h, B)        B concurrent streams; state fresh
+ *   aec_crn_stream_reset(h, b, st)   stream b's state fresh again (-1: all, and the hop counter)
  *   aec_crn_stream_step(h, mic, far, ld_in, out, ld_out, st)
  *        mic, far: device [B, ld_in] float32, hop k of every stream (samples
  *        256k .. 256k+255; zero-pad a final partial hop);
