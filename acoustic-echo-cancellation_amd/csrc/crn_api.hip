@@ -5,7 +5,11 @@
 // crn_host.h folds and packs from the parameter blob (the blob layout, the
 // float64 norm fold, the kernels' weight layouts, the MX-fp8 rows, the
 // per-layer rules and the workspace sizes all live there, GPU-free and tested
-// on the CPU), owns a grow-only workspace and sequences the launches.
+// on the CPU), owns a grow-only workspace and sequences the launches.  What
+// each launch reads and writes (the row GEMMs' geometry, the fused kernels'
+// level tables) and which kernel a config gets are crn_plan.h's, GPU-free and
+// tested the same way: here a plan gets its device pointers and is launched,
+// and the environment knobs the rules take are read.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -23,6 +27,7 @@
 #include "aec_tables.h"
 #include "crn_host.h"
 #include "crn_launch.h"
+#include "crn_plan.h"
 
 using crn::bf16_t;
 using namespace crn_host;
@@ -35,6 +40,29 @@ struct Packed : PackShape {
     float* bias = nullptr;      // [npad]
     uint8_t* wq = nullptr;      // dtype 2 (LSTM input projections, qualifying conv layers): e4m3 [npad8][kpad]
     uint8_t* wsc = nullptr;     //   and E8M0 scales [npad8][kpad / 32]
+};
+
+// Feature buffers of one pass over F frames (batch: F = B*Tmax; stream: F = B), sized by ws_bytes
+struct FeatureBufs {
+    void* x0 = nullptr;
+    std::vector<void*> cat;                        // index 1..L
+    void* gx = nullptr;
+    void* xn = nullptr;
+    float* mask = nullptr;
+    uint8_t* aq = nullptr;                         // dtype 2: quantized rows [rows][K] + scales [rows][K/32] (layers
+    uint8_t* as = nullptr;                         //   without a shadow)
+    std::vector<uint8_t*> cat8, cats;              // dtype 2: MX-fp8 shadows of cat[l] (e4m3 [F][bins][2 ch], E8M0 per
+                                                   //   32; null: none), see shadow_level
+    uint8_t* xn8 = nullptr;                        //   and of xn
+    uint8_t* xns = nullptr;
+};
+
+// split-K workspace of the MX conv GEMMs (per-hop streaming only; skp null: no split)
+struct SplitK {
+    float* skp = nullptr;                          // partial tiles
+    int* skc = nullptr;                            // tile counters
+    int64_t sk_bytes = 0;
+    int32_t skc_n = 0;
 };
 
 }  // namespace
@@ -50,19 +78,10 @@ struct aec_crn_handle : Net<Packed> {              // cfg, the derived sizes and
     bool have_params = false;
     // workspace
     int64_t ws_B = 0, ws_T = 0;
-    void* x0 = nullptr;
-    std::vector<void*> cat;                        // index 1..L
-    void* gx = nullptr;
+    FeatureBufs fb;
     void* y = nullptr;
-    void* xn = nullptr;
-    uint8_t* aq = nullptr;                         // dtype 2: quantized rows + scales (layers without a shadow)
-    uint8_t* as = nullptr;
-    std::vector<uint8_t*> cat8, cats;              // dtype 2: MX-fp8 shadows of cat[l] (null: none), see shadow_level
-    uint8_t* xn8 = nullptr;                        //   and of xn
-    uint8_t* xns = nullptr;
     float* cst = nullptr;
-    float* mask = nullptr;
-    float2* nrows = nullptr;                       // NLMS: packed mic / far rows [B][T][2][256]
+    float2* nrows = nullptr;                      // NLMS: packed mic / far rows [B][T][2][256]
     float2* espec = nullptr;                       //       error rows E [B][T][256]
     float2* ndummy = nullptr;                      //       [B][256] sink for frames past a stream's end
     int64_t* d_len = nullptr;
@@ -151,6 +170,41 @@ static aec_status load_params(aec_crn_handle* h, const float* params, size_t n) 
     return AEC_OK;
 }
 
+// One device buffer of an owner's `allocs` list; 0 bytes: the network has no such buffer (*p null).
+// zero: filled with zeros (the per-hop streaming state; the batch workspace is written before it is read)
+template <typename T>
+static hipError_t dev_alloc(T** p, size_t bytes, std::vector<void*>& allocs, bool zero) {
+    *p = nullptr;
+    if (bytes == 0) return hipSuccess;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(bytes, 16));
+    if (e == hipSuccess) {
+        allocs.push_back(*p);
+        if (zero) e = hipMemset(*p, 0, std::max<size_t>(bytes, 16));
+    }
+    return e;
+}
+
+static aec_status alloc_features(aec_crn_handle* h, FeatureBufs& fb, const WsBytes& wb, std::vector<void*>& allocs,
+                                 bool zero) {
+    CRN_TRY(h, dev_alloc(&fb.x0, wb.x0, allocs, zero));
+    fb.cat.assign(h->L + 1, nullptr);
+    fb.cat8.assign(h->L + 1, nullptr);
+    fb.cats.assign(h->L + 1, nullptr);
+    for (int l = 1; l <= h->L; ++l) {
+        CRN_TRY(h, dev_alloc(&fb.cat[l], wb.cat[l], allocs, zero));
+        CRN_TRY(h, dev_alloc(&fb.cat8[l], wb.cat8[l], allocs, zero));
+        CRN_TRY(h, dev_alloc(&fb.cats[l], wb.cats[l], allocs, zero));
+    }
+    CRN_TRY(h, dev_alloc(&fb.gx, wb.gx, allocs, zero));
+    CRN_TRY(h, dev_alloc(&fb.xn, wb.xn, allocs, zero));
+    CRN_TRY(h, dev_alloc(&fb.aq, wb.aq, allocs, zero));
+    CRN_TRY(h, dev_alloc(&fb.as, wb.as, allocs, zero));
+    CRN_TRY(h, dev_alloc(&fb.xn8, wb.xn8, allocs, zero));
+    CRN_TRY(h, dev_alloc(&fb.xns, wb.xns, allocs, zero));
+    CRN_TRY(h, dev_alloc(&fb.mask, wb.mask, allocs, zero));
+    return AEC_OK;
+}
+
 static aec_status ensure_ws(aec_crn_handle* h, int64_t B, int64_t T) {
     if (B <= h->ws_B && T <= h->ws_T) return AEC_OK;
     for (void* p : h->allocs) (void)hipFree(p);
@@ -159,35 +213,14 @@ static aec_status ensure_ws(aec_crn_handle* h, int64_t B, int64_t T) {
     h->last_B = 0;                                 // and the NLMS rows with it
     const int64_t nB = std::max<int64_t>(B, h->ws_B), nT = std::max<int64_t>(T, h->ws_T);
     const WsBytes wb = ws_bytes(*h, nB, nT);
-    auto alloc = [&](auto** p, size_t bytes) {     // 0 bytes: the network has no such buffer
-        *p = nullptr;
-        if (bytes == 0) return hipSuccess;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(bytes, 16));
-        if (e == hipSuccess) h->allocs.push_back(*p);
-        return e;
-    };
-    CRN_TRY(h, alloc(&h->x0, wb.x0));
-    h->cat.assign(h->L + 1, nullptr);
-    for (int l = 1; l <= h->L; ++l) CRN_TRY(h, alloc(&h->cat[l], wb.cat[l]));
-    CRN_TRY(h, alloc(&h->gx, wb.gx));
-    CRN_TRY(h, alloc(&h->y, wb.y));
-    CRN_TRY(h, alloc(&h->xn, wb.xn));
-    CRN_TRY(h, alloc(&h->aq, wb.aq));
-    CRN_TRY(h, alloc(&h->as, wb.as));
-    h->cat8.assign(h->L + 1, nullptr);
-    h->cats.assign(h->L + 1, nullptr);
-    for (int l = 1; l <= h->L; ++l) {
-        CRN_TRY(h, alloc(&h->cat8[l], wb.cat8[l]));
-        CRN_TRY(h, alloc(&h->cats[l], wb.cats[l]));
-    }
-    CRN_TRY(h, alloc(&h->xn8, wb.xn8));
-    CRN_TRY(h, alloc(&h->xns, wb.xns));
-    CRN_TRY(h, alloc(&h->cst, wb.cst));
-    CRN_TRY(h, alloc(&h->mask, wb.mask));
-    CRN_TRY(h, alloc(&h->d_len, wb.d_len));
-    CRN_TRY(h, alloc(&h->nrows, wb.nrows));
-    CRN_TRY(h, alloc(&h->espec, wb.espec));
-    CRN_TRY(h, alloc(&h->ndummy, wb.ndummy));
+    const aec_status s = alloc_features(h, h->fb, wb, h->allocs, false);
+    if (s != AEC_OK) return s;
+    CRN_TRY(h, dev_alloc(&h->y, wb.y, h->allocs, false));
+    CRN_TRY(h, dev_alloc(&h->cst, wb.cst, h->allocs, false));
+    CRN_TRY(h, dev_alloc(&h->d_len, wb.d_len, h->allocs, false));
+    CRN_TRY(h, dev_alloc(&h->nrows, wb.nrows, h->allocs, false));
+    CRN_TRY(h, dev_alloc(&h->espec, wb.espec, h->allocs, false));
+    CRN_TRY(h, dev_alloc(&h->ndummy, wb.ndummy, h->allocs, false));
     h->ws_B = nB;
     h->ws_T = nT;
     return AEC_OK;
@@ -204,48 +237,20 @@ static void mark(aec_crn_handle* h, hipStream_t st) {
     (void)hipEventRecord(h->ev[h->ev_used++], st);
 }
 
-// Feature buffers of one pass over F frames (batch: F = B*Tmax; stream: F = B)
-struct Bufs {
-    void* x0;
-    void* const* cat;       // [L+1], index 1..L
-    void* gx;
-    void* xn;
-    float* mask;
-    uint8_t* aq;            // dtype 2: quantized rows [rows][K] + scales [rows][K/32] (layers without a shadow)
-    uint8_t* as;
-    uint8_t* const* cat8;   // dtype 2: MX-fp8 shadows of cat[l] (e4m3 [F][bins][2 ch], E8M0 per 32), null: none
-    uint8_t* const* cats;
-    uint8_t* xn8;           //   and of xn
-    uint8_t* xns;
-    // split-K workspace of the MX conv GEMMs (per-hop streaming only; null: no split)
-    float* skp = nullptr;
-    int* skc = nullptr;
-    int64_t sk_bytes = 0;
-    int32_t skc_n = 0;
-};
-
-// an output with an MX-fp8 shadow
-template <typename T>
-static void set_shadow(crn::RowEpi& e, uint8_t* q8, uint8_t* qs) {
-    if (q8 && shadow_cols(e.N, sizeof(T))) {
-        e.q8 = q8;
-        e.qs = qs;
-    }
-}
-
 // dtype 2 GEMM over the implicit rows `a`: in place from the source's MX-fp8 shadow
-// (q8 / qs, written by its producers), else quantised into bf.aq / bf.as first
+// (q8 / qs, written by its producers), else quantised into bf.aq / bf.as first; sk: the conv
+// layers' split-K workspace (null: no split)
 template <typename T>
 static aec_status mx8_gemm(aec_crn_handle* h, const crn::RowSrc& a, const uint8_t* q8, const uint8_t* qs,
-                           const Bufs& bf, const uint8_t* wq, const uint8_t* wsc, int K, const crn::RowEpi& e0, int npad,
-                           hipStream_t st, bool conv = false) {
+                           const FeatureBufs& bf, const uint8_t* wq, const uint8_t* wsc, int K, const crn::RowEpi& e0,
+                           int npad, hipStream_t st, const SplitK* sk = nullptr) {
     crn::RowEpi e = e0;
-    if (conv && bf.skp) {
+    if (sk && sk->skp) {
         e.ksplit = conv_ksplit(K);
-        e.skp = bf.skp;
-        e.skc = bf.skc;
-        e.sk_bytes = bf.sk_bytes;
-        e.skc_n = bf.skc_n;
+        e.skp = sk->skp;
+        e.skc = sk->skc;
+        e.sk_bytes = sk->sk_bytes;
+        e.skc_n = sk->skc_n;
     }
     if (q8) {
         crn::RowSrc a8 = a;
@@ -258,248 +263,149 @@ static aec_status mx8_gemm(aec_crn_handle* h, const crn::RowSrc& a, const uint8_
     return AEC_OK;
 }
 
+// a row-GEMM plan's pointers: the source map, the destination (with its MX-fp8 shadow when the plan
+// says the epilogue writes one) and the bias
+static void attach(Rows& r, const void* src, void* out, const float* bias, uint8_t* q8 = nullptr, uint8_t* qs = nullptr) {
+    r.a.src = src;
+    r.e.out = out;
+    r.e.bias = bias;
+    if (r.shadow) {
+        r.e.q8 = q8;
+        r.e.qs = qs;
+    }
+}
+
+// One conv layer's row GEMM: the scaled-MFMA GEMM on e4m3 rows + E8M0 scales when the layer has MX
+// rows (dtype 2, see conv_mx8; in8 / ins: the source map's shadow or null), else bf16 / f32
+template <typename T>
+static aec_status conv_gemm(aec_crn_handle* h, const Packed& pk, const Rows& r, const uint8_t* in8, const uint8_t* ins,
+                            const FeatureBufs& bf, const SplitK* sk, hipStream_t st) {
+    if (pk.wq) return mx8_gemm<T>(h, r.a, in8, ins, bf, pk.wq, pk.wsc, pk.kpad, r.e, pk.npad8, st, sk);
+    CRN_TRY(h, (crn::launch_gemm_rows<T, T>(r.a, reinterpret_cast<const T*>(pk.w), pk.kpad,
+                                             (int)(pk.kpad * sizeof(T) / crn::kStageBytes), r.e, pk.npad, st)));
+    return AEC_OK;
+}
+
+// encoder level i / decoder level cl of a fused kernel's level table (bf16 storage)
+static crn::StreamEncLevel enc_level(const aec_crn_handle* h, const FeatureBufs& bf, int i) {
+    const Packed& pk = h->enc[i];
+    crn::StreamEncLevel L = enc_level_entry(*h, i);
+    L.w = reinterpret_cast<const bf16_t*>(pk.w);
+    L.bias = pk.bias;
+    L.out = reinterpret_cast<bf16_t*>(bf.cat[i + 1]);
+    if (shadow_out(*h, i + 1, pk.N)) {
+        L.q8 = bf.cat8[i + 1];
+        L.qs = bf.cats[i + 1];
+    }
+    return L;
+}
+static crn::StreamDecLevel dec_level(const aec_crn_handle* h, const FeatureBufs& bf, int cl) {
+    const Packed& pk = h->decf[h->L - cl];
+    crn::StreamDecLevel L = dec_level_entry(*h, cl);
+    L.w = reinterpret_cast<const bf16_t*>(pk.w);
+    L.bias = pk.bias;
+    L.src = reinterpret_cast<const bf16_t*>(bf.cat[cl]);
+    return L;
+}
+
 // Batch forward: encoder levels 0-3 in one launch (crn_enc_batch_kernel) when the handle's
 // levels have its shapes (bf16 storage, bf16 GEMMs on those levels); AEC_CRN_BATCH_ENC=0
 // restores the four row GEMMs (A/B and the bit-equality test), =2 makes a handle whose levels do
 // not fit fail with AEC_ERR_UNSUPPORTED (the test's proof that the fused path ran).  Returns the
 // levels it ran.
-template <typename T>
-static int run_enc_batch_try(aec_crn_handle* h, const Bufs& bf, int64_t F, hipStream_t st, aec_status* s);
-template <typename T>
-static int run_enc_batch(aec_crn_handle* h, const Bufs& bf, int64_t F, hipStream_t st, aec_status* s) {
+static int run_enc_batch(aec_crn_handle* h, const FeatureBufs& bf, int64_t F, hipStream_t st, aec_status* s) {
     *s = AEC_OK;
     const int mode = AEC_MODE_KNOB("AEC_CRN_BATCH_ENC", 1);
     if (mode == 0) return 0;
-    const int n = run_enc_batch_try<T>(h, bf, F, st, s);
-    if (n == 0 && *s == AEC_OK && mode == 2) {
-        h->err = "AEC_CRN_BATCH_ENC=2: the encoder levels do not fit crn_enc_batch_kernel";
-        *s = AEC_ERR_UNSUPPORTED;
-    }
-    return n;
-}
-template <typename T>
-static int run_enc_batch_try(aec_crn_handle* h, const Bufs& bf, int64_t F, hipStream_t st, aec_status* s) {
-    if (sizeof(T) != 2 || h->es != 2 || h->L < 5) return 0;
-    const int* ch = h->cfg.conv_channels;
     crn::EncBatchArgs ea{};
     ea.x0 = reinterpret_cast<const bf16_t*>(bf.x0);
     ea.F = F;
-    for (int i = 0; i < 4; ++i) {
-        const Packed& pk = h->enc[i];
-        if (pk.wq || pk.act != 1) return 0;
-        crn::StreamEncLevel& L = ea.lev[i];
-        L.w = reinterpret_cast<const bf16_t*>(pk.w);
-        L.bias = pk.bias;
-        L.alpha = pk.alpha;
-        L.kpad = pk.kpad;
-        L.N = pk.N;
-        L.nchunk = (pk.K + 31) / 32;
-        L.cin_shift = ilog2(i == 0 ? 8 : ch[i]);
-        L.out = reinterpret_cast<bf16_t*>(bf.cat[i + 1]);
-        L.ldo = 2 * ch[i + 1];
-        L.choff = ch[i + 1];
-        if (bf.cat8 && bf.cat8[i + 1] && shadow_cols(pk.N, sizeof(T))) {
-            L.q8 = bf.cat8[i + 1];
-            L.qs = bf.cats[i + 1];
+    const int n = enc_batch_levels(*h);
+    for (int i = 0; i < n; ++i) ea.lev[i] = enc_level(h, bf, i);
+    if (n == 0 || !crn::enc_batch_ok(ea)) {
+        if (mode == 2) {
+            h->err = "AEC_CRN_BATCH_ENC=2: the encoder levels do not fit crn_enc_batch_kernel";
+            *s = AEC_ERR_UNSUPPORTED;
         }
-        if (pk.N != ch[i + 1]) return 0;
+        return 0;
     }
-    if (!crn::enc_batch_ok(ea)) return 0;
     const hipError_t e = crn::launch_enc_batch(ea, st);
     if (e != hipSuccess) {
         h->err = std::string("launch_enc_batch: ") + hipGetErrorString(e);
         *s = e == hipErrorOutOfMemory ? AEC_ERR_OOM : AEC_ERR_HIP;
         return 0;
     }
-    return 4;
+    return n;
 }
 
 template <typename T>
-static aec_status run_encoder(aec_crn_handle* h, const Bufs& bf, int64_t F, hipStream_t st, int first = 0,
-                              bool batch = false) {
-    using crn::RowEpi;
-    using crn::RowSrc;
+static aec_status run_encoder(aec_crn_handle* h, const FeatureBufs& bf, int64_t F, hipStream_t st, int first = 0,
+                              bool batch = false, const SplitK* sk = nullptr) {
     aec_status s = AEC_OK;
-    const int* ch = h->cfg.conv_channels;
     if (batch && first == 0) {
-        first = run_enc_batch<T>(h, bf, F, st, &s);
+        first = run_enc_batch(h, bf, F, st, &s);
         if (s != AEC_OK) return s;
     }
     for (int i = first; i < h->L; ++i) {
-        const int Fin = 256 >> i, Fo = Fin / 2;
-        const int cin = i == 0 ? 8 : ch[i];
-        const int64_t ld_in = i == 0 ? 8 : 2 * ch[i];
-        const int64_t choff = i == 0 ? 0 : ch[i];
         const Packed& pk = h->enc[i];
-        RowSrc a{};
-        a.src = i == 0 ? bf.x0 : bf.cat[i];
-        a.M = F * Fo;
-        a.K = pk.K;
-        a.rshift = ilog2(Fo);
-        a.rs_hi = Fin * ld_in;
-        a.rs_lo = 2 * ld_in;
-        a.kshift = ilog2(cin);
-        a.ks = ld_in;
-        a.pmul = 2;
-        a.padd = -2;
-        a.plim = Fin;
-        a.base_off = choff - 2 * ld_in;
-        a.src_elems = F * Fin * ld_in;
-        const int64_t ldo = 2 * ch[i + 1];
-        RowEpi e{bf.cat[i + 1], a.M, pk.N, a.rshift, Fo * ldo, ldo, ch[i + 1], pk.bias, pk.alpha, pk.act};
-        set_shadow<T>(e, bf.cat8[i + 1], bf.cats[i + 1]);
-        if (pk.wq) {                       // dtype 2: e4m3 rows + E8M0 scales, scaled-MFMA GEMM
-            s = mx8_gemm<T>(h, a, i > 0 ? bf.cat8[i] : nullptr, i > 0 ? bf.cats[i] : nullptr, bf, pk.wq, pk.wsc,
-                            pk.kpad, e, pk.npad8, st, true);
-            if (s != AEC_OK) return s;
-            continue;
-        }
-        CRN_TRY(h, (crn::launch_gemm_rows<T, T>(a, reinterpret_cast<const T*>(pk.w), pk.kpad,
-                                                 (int)(pk.kpad * sizeof(T) / crn::kStageBytes), e, pk.npad, st)));
+        Rows r = enc_rows(*h, i, F);
+        attach(r, i == 0 ? bf.x0 : bf.cat[i], bf.cat[i + 1], pk.bias, bf.cat8[i + 1], bf.cats[i + 1]);
+        s = conv_gemm<T>(h, pk, r, bf.cat8[i], bf.cats[i], bf, sk, st);   // cat8[0]: null (X0 has no shadow)
+        if (s != AEC_OK) return s;
     }
     return AEC_OK;
 }
 
 // LSTM layer l input projection for F frames -> bf.gx [F][S][CELLS*4H]
 template <typename T>
-static aec_status run_lstm_input(aec_crn_handle* h, const Bufs& bf, int l, int64_t F, hipStream_t st) {
-    using crn::RowEpi;
-    using crn::RowSrc;
-    const int* ch = h->cfg.conv_channels;
-    const int L = h->L, H = h->H, S = h->S, C = h->CELLS, D = h->D, Q = h->Q;
-    RowSrc a{};
-    int64_t ld_in, choff;
-    if (l == 0) {
-        a.src = bf.cat[L];
-        ld_in = 2 * ch[L];
-        choff = ch[L];
-    } else {
-        a.src = bf.xn;
-        ld_in = (int64_t)S * Q;
-        choff = 0;
-    }
-    a.M = F * S;
-    a.K = H;
-    a.rshift = ilog2(S);
-    a.rs_hi = D * ld_in;
-    a.rs_lo = Q;
-    a.kshift = ilog2(Q);
-    a.ks = ld_in;
-    a.pmul = 0;
-    a.padd = 0;
-    a.plim = D;
-    a.base_off = choff;
-    a.src_elems = F * D * ld_in;
+static aec_status run_lstm_input(aec_crn_handle* h, const FeatureBufs& bf, int l, int64_t F, hipStream_t st) {
     const Packed& ih = h->lih[l];
-    RowEpi e{bf.gx, a.M, ih.N, 0, (int64_t)C * 4 * H, 0, 0, ih.bias, 0.f, 0};
+    Rows r = lstm_in_rows(*h, l, F);
+    attach(r, l == 0 ? bf.cat[h->L] : bf.xn, bf.gx, ih.bias);
     if (h->mx8)                            // e4m3 rows + E8M0 scales, scaled-MFMA GEMM
-        return mx8_gemm<T>(h, a, l == 0 ? bf.cat8[L] : bf.xn8, l == 0 ? bf.cats[L] : bf.xns, bf, ih.wq, ih.wsc,
-                           ih.kpad, e, ih.npad, st);
-    CRN_TRY(h, (crn::launch_gemm_rows<T, T>(a, reinterpret_cast<const T*>(ih.w), ih.kpad,
-                                             (int)(ih.kpad * sizeof(T) / crn::kStageBytes), e, ih.npad, st)));
+        return mx8_gemm<T>(h, r.a, l == 0 ? bf.cat8[h->L] : bf.xn8, l == 0 ? bf.cats[h->L] : bf.xns, bf, ih.wq, ih.wsc,
+                           ih.kpad, r.e, ih.npad, st);
+    CRN_TRY(h, (crn::launch_gemm_rows<T, T>(r.a, reinterpret_cast<const T*>(ih.w), ih.kpad,
+                                             (int)(ih.kpad * sizeof(T) / crn::kStageBytes), r.e, ih.npad, st)));
     return AEC_OK;
 }
 
 // NavieComplexLSTM combination of layer l's h rows y [F][C][S][H] -> the next
 // layer's input (xn) or the decoder's dec half of cat[L]
 template <typename T>
-static aec_status run_lstm_combine(aec_crn_handle* h, const Bufs& bf, int l, const void* y, int64_t F,
+static aec_status run_lstm_combine(aec_crn_handle* h, const FeatureBufs& bf, int l, const void* y, int64_t F,
                                    hipStream_t st) {
-    const int* ch = h->cfg.conv_channels;
-    const int L = h->L, S = h->S, Q = h->Q;
     const bool last = l + 1 == h->nrnn;
-    T* dst = reinterpret_cast<T*>(last ? bf.cat[L] : bf.xn);
-    const int64_t ldd = last ? 2 * ch[L] : (int64_t)S * Q;
-    uint8_t* q8 = sizeof(T) == 2 ? (last ? bf.cat8[L] : bf.xn8) : nullptr;
-    uint8_t* qs = sizeof(T) == 2 ? (last ? bf.cats[L] : bf.xns) : nullptr;
-    CRN_TRY(h, crn::launch_lstm_combine<T>(reinterpret_cast<const T*>(y), dst, F, h->H, h->CELLS, S, ilog2(Q),
-                                           h->D * ldd, ldd, st, q8, qs));
+    const CombineDst c = combine_dst(*h, l);
+    T* dst = reinterpret_cast<T*>(last ? bf.cat[h->L] : bf.xn);
+    uint8_t* q8 = sizeof(T) == 2 ? (last ? bf.cat8[h->L] : bf.xn8) : nullptr;
+    uint8_t* qs = sizeof(T) == 2 ? (last ? bf.cats[h->L] : bf.xns) : nullptr;
+    CRN_TRY(h, crn::launch_lstm_combine<T>(reinterpret_cast<const T*>(y), dst, F, h->H, h->CELLS, h->S, c.dshift, c.ldf,
+                                           c.ldd, st, q8, qs));
     return AEC_OK;
 }
 
+// decoder levels d0 .. nd-1 (cl = L - d) as row GEMMs: both parities in one GEMM where the level
+// has a fused operand (pack_decoder_fused), else one GEMM per parity
 template <typename T>
-static aec_status run_decoder(aec_crn_handle* h, const Bufs& bf, int64_t F, hipStream_t st, int nd = -1, int d0 = 0) {
-    using crn::RowEpi;
-    using crn::RowSrc;
-    const int* ch = h->cfg.conv_channels;
-    const int L = h->L;
-    for (int d = d0; d < (nd < 0 ? L : nd); ++d) {
-        const int cl = L - d;
-        const int Fin = 256 >> cl, Fo = 2 * Fin;
-        const int64_t ld_in = 2 * ch[cl];
-        if (h->decf[d].w) {                // both parities in one GEMM (pack_decoder_fused)
-            const Packed& pk = h->decf[d];
-            RowSrc a{};
-            a.src = bf.cat[cl];
-            a.M = F * Fin;
-            a.K = pk.K;
-            a.rshift = ilog2(Fin);
-            a.rs_hi = Fin * ld_in;
-            a.rs_lo = ld_in;
-            a.kshift = ilog2(ld_in);
-            a.ks = ld_in;
-            a.pmul = 1;
-            a.padd = -1;
-            a.plim = Fin;
-            a.base_off = -ld_in;
-            a.src_elems = F * Fin * ld_in;
-            if (cl == 1) {                 // the mask: row (f, i) -> bins 2i, 2i + 1 = 4 adjacent floats
-                RowEpi e{bf.mask, a.M, pk.N, a.rshift, (int64_t)Fo * 2, 4, 0, pk.bias, pk.alpha, pk.act};
-                CRN_TRY(h, (crn::launch_gemm_rows<T, float>(a, reinterpret_cast<const T*>(pk.w), pk.kpad,
-                                                             (int)(pk.kpad * sizeof(T) / crn::kStageBytes), e,
+static aec_status run_decoder(aec_crn_handle* h, const FeatureBufs& bf, int64_t F, hipStream_t st, int nd = -1, int d0 = 0,
+                              const SplitK* sk = nullptr) {
+    for (int d = d0; d < (nd < 0 ? h->L : nd); ++d) {
+        const int cl = h->L - d;
+        const bool fused = h->decf[d].w != nullptr;
+        for (int par = fused ? kParFused : 0; par < (fused ? kParFused + 1 : 2); ++par) {
+            const Packed& pk = fused ? h->decf[d] : h->dec[2 * d + par];
+            Rows r = dec_rows(*h, d, par, F);
+            if (cl == 1) {                 // the f32 mask
+                attach(r, bf.cat[cl], bf.mask, pk.bias);
+                CRN_TRY(h, (crn::launch_gemm_rows<T, float>(r.a, reinterpret_cast<const T*>(pk.w), pk.kpad,
+                                                             (int)(pk.kpad * sizeof(T) / crn::kStageBytes), r.e,
                                                              pk.npad, st)));
                 continue;
             }
-            const int64_t ldo = 2 * ch[cl - 1];
-            RowEpi e{bf.cat[cl - 1], a.M, pk.N, a.rshift, Fo * ldo, 2 * ldo, 0, pk.bias, pk.alpha, pk.act};
-            e.nsplit = pk.N / 2;
-            e.split_add = ldo;
-            set_shadow<T>(e, bf.cat8[cl - 1], bf.cats[cl - 1]);
-            if (pk.wq) {                   // dtype 2 (see conv_mx8)
-                const aec_status s = mx8_gemm<T>(h, a, bf.cat8[cl], bf.cats[cl], bf, pk.wq, pk.wsc, pk.kpad, e,
-                                                 pk.npad8, st, true);
-                if (s != AEC_OK) return s;
-                continue;
-            }
-            CRN_TRY(h, (crn::launch_gemm_rows<T, T>(a, reinterpret_cast<const T*>(pk.w), pk.kpad,
-                                                     (int)(pk.kpad * sizeof(T) / crn::kStageBytes), e, pk.npad, st)));
-            continue;
-        }
-        for (int par = 0; par < 2; ++par) {
-            const Packed& pk = h->dec[2 * d + par];
-            RowSrc a{};
-            a.src = bf.cat[cl];
-            a.M = F * Fin;
-            a.K = pk.K;
-            a.rshift = ilog2(Fin);
-            a.rs_hi = Fin * ld_in;
-            a.rs_lo = ld_in;
-            a.kshift = ilog2(ld_in);
-            a.ks = ld_in;
-            a.pmul = 1;
-            a.padd = par == 0 ? -1 : 0;
-            a.plim = Fin;
-            a.base_off = a.padd * ld_in;
-            a.src_elems = F * Fin * ld_in;
-            if (cl != 1) {
-                const int64_t ldo = 2 * ch[cl - 1];
-                RowEpi e{bf.cat[cl - 1], a.M, pk.N, a.rshift, Fo * ldo, 2 * ldo, par * ldo, pk.bias, pk.alpha, pk.act};
-                set_shadow<T>(e, bf.cat8[cl - 1], bf.cats[cl - 1]);
-                if (pk.wq) {               // dtype 2 (see conv_mx8)
-                    const aec_status s = mx8_gemm<T>(h, a, bf.cat8[cl], bf.cats[cl], bf, pk.wq, pk.wsc, pk.kpad, e,
-                                                     pk.npad8, st, true);
-                    if (s != AEC_OK) return s;
-                    continue;
-                }
-                CRN_TRY(h, (crn::launch_gemm_rows<T, T>(a, reinterpret_cast<const T*>(pk.w), pk.kpad,
-                                                         (int)(pk.kpad * sizeof(T) / crn::kStageBytes), e, pk.npad,
-                                                         st)));
-            } else {
-                RowEpi e{bf.mask, a.M, pk.N, a.rshift, (int64_t)Fo * 2, 4, (int64_t)par * 2, pk.bias, pk.alpha, pk.act};
-                CRN_TRY(h, (crn::launch_gemm_rows<T, float>(a, reinterpret_cast<const T*>(pk.w), pk.kpad,
-                                                             (int)(pk.kpad * sizeof(T) / crn::kStageBytes), e,
-                                                             pk.npad, st)));
-            }
+            attach(r, bf.cat[cl], bf.cat[cl - 1], pk.bias, bf.cat8[cl - 1], bf.cats[cl - 1]);
+            const aec_status s = conv_gemm<T>(h, pk, r, bf.cat8[cl], bf.cats[cl], bf, sk, st);
+            if (s != AEC_OK) return s;
         }
     }
     return AEC_OK;
@@ -535,7 +441,7 @@ static aec_status run_persist(aec_crn_handle* h, int l, int32_t B, int64_t Tmax,
         const int nb = std::min<int32_t>(chunk, B - b0);
         crn::PersistArgs a{};
         a.whh = reinterpret_cast<const bf16_t*>(h->lhh[l].w);
-        a.gx = reinterpret_cast<const bf16_t*>(h->gx);
+        a.gx = reinterpret_cast<const bf16_t*>(h->fb.gx);
         a.y = reinterpret_cast<bf16_t*>(h->y);
         a.sync = h->psync;
         a.B = B;
@@ -585,34 +491,18 @@ static aec_status persist_wait(aec_crn_handle* h) {
 // Batch forward, bf16 storage: decoder levels cl = 3, 2 in one launch (crn_dec_batch_kernel) when
 // their shapes fit; AEC_CRN_BATCH_DEC=0 restores the two row GEMMs, =2 fails the call unless the
 // fused kernel ran (the bit-equality test).  Returns true when it ran.
-template <typename T>
-static bool run_dec_batch(aec_crn_handle* h, const Bufs& bf, int64_t F, hipStream_t st, aec_status* s) {
+static bool run_dec_batch(aec_crn_handle* h, const FeatureBufs& bf, int64_t F, hipStream_t st, aec_status* s) {
     *s = AEC_OK;
     const int mode = AEC_MODE_KNOB("AEC_CRN_BATCH_DEC", 1);
     if (mode == 0) return false;
-    bool ok = sizeof(T) == 2 && h->es == 2 && h->L >= 4;
+    bool ok = dec_batch_fits(*h);
     crn::DecBatchArgs da{};
     if (ok) {
-        const int* ch = h->cfg.conv_channels;
         da.F = F;
-        for (int l = 0; l < 2; ++l) {
-            const int cl = 3 - l, d = h->L - cl;
-            const Packed& pk = h->decf[d];
-            crn::StreamDecLevel& L = da.lev[l];
-            if (!pk.w || pk.wq || pk.N != 2 * ch[cl - 1]) ok = false;
-            L.w = reinterpret_cast<const bf16_t*>(pk.w);
-            L.bias = pk.bias;
-            L.alpha = pk.alpha;
-            L.act = pk.act;
-            L.kpad = pk.kpad;
-            L.N = pk.N;
-            L.nchunk = (pk.K + 31) / 32;
-            L.cin_shift = ilog2(2 * ch[cl]);
-            L.src = reinterpret_cast<const bf16_t*>(bf.cat[cl]);
-        }
+        for (int l = 0; l < 2; ++l) da.lev[l] = dec_level(h, bf, 3 - l);
         da.out = reinterpret_cast<bf16_t*>(bf.cat[1]);
-        da.ldo1 = 2 * ch[1];
-        ok = ok && crn::dec_batch_ok(da);
+        da.ldo1 = 2 * h->cfg.conv_channels[1];
+        ok = crn::dec_batch_ok(da);
     }
     if (!ok) {
         if (mode == 2) {
@@ -634,14 +524,13 @@ template <typename T>
 static aec_status run(aec_crn_handle* h, const float* mic, const float* far, int32_t B, int64_t ld, int64_t Tmax,
                       float* out, int64_t ld_out, float* spec, float* mask_out, hipStream_t st) {
     const int64_t BT = (int64_t)B * Tmax;
-    const Bufs bf{h->x0, h->cat.data(), h->gx, h->xn, h->mask, h->aq, h->as, h->cat8.data(), h->cats.data(), h->xn8,
-                  h->xns};
+    const FeatureBufs& bf = h->fb;
     const int H = h->H, S = h->S, C = h->CELLS;
     const bool persist = sizeof(T) == 2 && h->persist && h->psync && crn::persist_supported(H, C, S, h->num_cus);
     mark(h, st);
     // front: X0 [Tmax][B][256][8]
     const aec_crn_config& c = h->cfg;
-    crn::FrontArgs fa{mic, far, ld, h->d_len, Tmax, h->d_tab, h->x0, nullptr};
+    crn::FrontArgs fa{mic, far, ld, h->d_len, Tmax, h->d_tab, bf.x0, nullptr};
     if (c.nlms_taps > 0) fa.rows = h->nrows;
     CRN_TRY(h, crn::launch_front<T>(fa, B, st));
     if (c.nlms_taps > 0) {   // canceller: rows -> E rows (one block per stream) -> X0
@@ -651,7 +540,7 @@ static aec_status run(aec_crn_handle* h, const float* mic, const float* far, int
         else
             CRN_TRY(h, aec::launch_nlms_recursion(h->nrows, h->espec, h->d_len, Tmax, c.nlms_taps, c.nlms_mu, c.nlms_beta,
                                                   c.nlms_delta, 0, B, h->ndummy, st));
-        crn::RowsX0Args xa{h->nrows, h->espec, h->d_len, Tmax, h->x0, B};
+        crn::RowsX0Args xa{h->nrows, h->espec, h->d_len, Tmax, bf.x0, B};
         CRN_TRY(h, crn::launch_rows_x0<T>(xa, st));
     }
     mark(h, st);
@@ -670,7 +559,7 @@ static aec_status run(aec_crn_handle* h, const float* mic, const float* far, int
             continue;
         }
         for (int64_t t = 0; t < Tmax; ++t) {
-            crn::StepArgs sa{h->lhh[l].w, reinterpret_cast<const T*>(h->gx) + t * gstride,
+            crn::StepArgs sa{h->lhh[l].w, reinterpret_cast<const T*>(bf.gx) + t * gstride,
                              reinterpret_cast<const T*>(h->y) + (t > 0 ? t - 1 : 0) * ystride,
                              reinterpret_cast<T*>(h->y) + t * ystride, h->cst, B, H, t == 0, 0};
             CRN_TRY(h, crn::launch_lstm_step<T>(sa, C, S, st));
@@ -684,26 +573,25 @@ static aec_status run(aec_crn_handle* h, const float* mic, const float* far, int
     // bf16: the mask level runs inside the back kernel (no f32 mask round trip) unless the
     // caller wants the mask itself (AEC_CRN_BACK_MASK=0: the row GEMM, A/B and bit-equality)
     const Packed& pm = h->decf[h->L - 1];
-    const bool mask_in_back = sizeof(T) == 2 && AEC_MODE_KNOB("AEC_CRN_BACK_MASK", 1) != 0 && pm.w && !mask_out &&
-                              (out || spec) && pm.N == 4 && pm.kpad <= 128 && pm.kpad % 32 == 0 && pm.act != 1;
+    const bool mask_in_back = mask_in_back_ok(*h, AEC_MODE_KNOB("AEC_CRN_BACK_MASK", 1), mask_out != nullptr, out || spec);
     {
         // decoder levels cl = L .. 4 as row GEMMs, cl = 3, 2 fused when they fit, then the mask
         // level (cl = 1) as a GEMM unless the back kernel computes it
         const int Ld = h->L, d3 = std::max(0, Ld - 3);
         s = run_decoder<T>(h, bf, BT, st, d3);
         if (s != AEC_OK) return s;
-        const bool fused = run_dec_batch<T>(h, bf, BT, st, &s);
+        const bool fused = run_dec_batch(h, bf, BT, st, &s);
         if (s != AEC_OK) return s;
         s = run_decoder<T>(h, bf, BT, st, mask_in_back ? Ld - 1 : Ld, fused ? Ld - 1 : d3);
         if (s != AEC_OK) return s;
     }
     mark(h, st);
     if (out || spec) {
-        crn::BackArgs ba{mic, ld, h->d_len, Tmax, h->d_tab, reinterpret_cast<const float2*>(h->mask), out, ld_out,
+        crn::BackArgs ba{mic, ld, h->d_len, Tmax, h->d_tab, reinterpret_cast<const float2*>(bf.mask), out, ld_out,
                          reinterpret_cast<float2*>(spec)};
         if (c.nlms_taps > 0) ba.espec = h->espec;
         if (mask_in_back) {
-            ba.dm_in = reinterpret_cast<const bf16_t*>(h->cat[1]);
+            ba.dm_in = reinterpret_cast<const bf16_t*>(bf.cat[1]);
             ba.dm_w = reinterpret_cast<const bf16_t*>(pm.w);
             ba.dm_bias = pm.bias;
             ba.dm_kpad = pm.kpad;
@@ -714,7 +602,7 @@ static aec_status run(aec_crn_handle* h, const float* mic, const float* far, int
     }
     if (mask_out)   // internal frames are t-major ([Tmax][B]); the ABI's mask is [B][Tmax]
         for (int b = 0; b < B; ++b)
-            CRN_TRY(h, hipMemcpy2DAsync(mask_out + (size_t)b * Tmax * 512, 512 * sizeof(float), h->mask + (size_t)b * 512,
+            CRN_TRY(h, hipMemcpy2DAsync(mask_out + (size_t)b * Tmax * 512, 512 * sizeof(float), bf.mask + (size_t)b * 512,
                                         (size_t)B * 512 * sizeof(float), 512 * sizeof(float), (size_t)Tmax,
                                         hipMemcpyDeviceToDevice, st));
     mark(h, st);
@@ -732,23 +620,11 @@ struct StreamState {
     int graph_mode = 0;
     int64_t graph_replays = 0, direct_hops = 0;
     std::vector<void*> allocs;
-    void* x0 = nullptr;
-    std::vector<void*> cat;
-    void* gx = nullptr;
-    void* xn = nullptr;
-    float* mask = nullptr;
-    uint8_t* aq = nullptr;               // dtype 2 (see Bufs)
-    uint8_t* as = nullptr;
-    std::vector<uint8_t*> cat8, cats;
-    uint8_t* xn8 = nullptr;
-    uint8_t* xns = nullptr;
+    FeatureBufs fb;                      // one frame per stream
     void* xnb = nullptr;                 // MX layer step, rnn_layers >= 3: the second xn set (bf16 rows,
     uint8_t* xn8b = nullptr;             //   e4m3 shadow, scales) the odd middle layers write
     uint8_t* xnsb = nullptr;
-    float* skp = nullptr;                // split-K partial tiles / tile counters of the MX conv GEMMs (Bufs)
-    int* skc = nullptr;
-    int64_t sk_bytes = 0;
-    int32_t skc_n = 0;
+    SplitK sk;                           // of the MX conv GEMMs
     void* ring_y[8][2] = {};             // per LSTM layer: h ring (two frames)
     uint8_t* ring_q[8][2] = {};          // dtype 2 MX layer step: h ring as e4m3 [B][C][S][H] + E8M0 [B][C][S][H/32]
     uint8_t* ring_s[8][2] = {};
@@ -817,61 +693,27 @@ static hipGraphNode_t last_node(hipStream_t st) {
 // against [W_ih | W_hh] on the scaled MFMA, the cell update and the combination.  x is read
 // in place from its MX-fp8 shadow (the encoder's / previous combination's epilogue), or,
 // without one (AEC_CRN_MX8_SHADOW=0), quantised first into bf.aq / bf.as by the same rule
-// (*quant: that pass's rows).  A middle layer (neither first nor last, rnn_layers >= 3) reads
+// (mx_step_plan).  A middle layer (neither first nor last, rnn_layers >= 3) reads
 // its input from one xn set and writes the other: blocks that finish early would otherwise
 // overwrite rows other blocks of the same launch still load.
-static void mx_step_args(aec_crn_handle* h, const StreamState& ss, const Bufs& bf, int l, int par,
-                         crn::StepMxArgs& ma, crn::RowSrc* quant) {
-    const int* ch = h->cfg.conv_channels;
-    const int L = h->L, H = h->H, S = h->S, D = h->D, Q = h->Q, B = ss.B;
+static aec_status run_lstm_mx_step(aec_crn_handle* h, StreamState& ss, int l, int par, hipStream_t st) {
+    const FeatureBufs& bf = ss.fb;
+    const int L = h->L;
     const bool last = l + 1 == h->nrnn;
     const bool in_b = l > 0 && ((l - 1) & 1), out_b = (l & 1) != 0;
-    void* xn_in = in_b ? ss.xnb : bf.xn;
-    void* xn_out = out_b ? ss.xnb : bf.xn;
-    uint8_t* xn8_in = in_b ? ss.xn8b : bf.xn8;
-    uint8_t* xns_in = in_b ? ss.xnsb : bf.xns;
-    ma = crn::StepMxArgs{};
+    MxStep m = mx_step_plan(*h, l, ss.B);
+    crn::StepMxArgs& ma = m.ma;
     ma.wq = h->lcat[l].wq;
     ma.wsc = h->lcat[l].wsc;
     ma.bias = h->lih[l].bias;
-    // x rows (b, s): the bf16 GEMM's implicit LSTM-input rows (run_lstm_input)
-    const int64_t ld_in = l == 0 ? 2 * ch[L] : (int64_t)S * Q;
-    const int64_t choff = l == 0 ? ch[L] : 0;
-    const uint8_t* x8 = l == 0 ? bf.cat8[L] : xn8_in;
-    const uint8_t* xs = l == 0 ? bf.cats[L] : xns_in;
-    if (quant) *quant = crn::RowSrc{};
-    if (x8) {
-        ma.xq = x8;
-        ma.xs = xs;
-        ma.x_f = D * ld_in;
-        ma.x_s = Q;
-        ma.x_t = ld_in;
-        ma.x_sh = ilog2(Q);
-        ma.x_0 = choff;
-        ma.x_elems = (int64_t)B * D * ld_in;
+    if (m.shadow_in) {
+        ma.xq = l == 0 ? bf.cat8[L] : in_b ? ss.xn8b : bf.xn8;
+        ma.xs = l == 0 ? bf.cats[L] : in_b ? ss.xnsb : bf.xns;
     } else {
-        if (quant) {
-            crn::RowSrc& a = *quant;
-            a.src = l == 0 ? bf.cat[L] : xn_in;
-            a.M = (int64_t)B * S;
-            a.K = H;
-            a.rshift = ilog2(S);
-            a.rs_hi = D * ld_in;
-            a.rs_lo = Q;
-            a.kshift = ilog2(Q);
-            a.ks = ld_in;
-            a.plim = D;
-            a.base_off = choff;
-            a.src_elems = (int64_t)B * D * ld_in;
-        }
+        m.quant.src = l == 0 ? bf.cat[L] : in_b ? ss.xnb : bf.xn;
+        CRN_TRY(h, crn::launch_mx8_quant(m.quant, bf.aq, bf.as, st));
         ma.xq = bf.aq;                              // dense rows [(b, s)][H]
         ma.xs = bf.as;
-        ma.x_f = (int64_t)S * H;
-        ma.x_s = H;
-        ma.x_t = 0;
-        ma.x_sh = ilog2(H);
-        ma.x_0 = 0;
-        ma.x_elems = (int64_t)B * S * H;
     }
     ma.hq_prev = ss.ring_q[l][1 - par];
     ma.hs_prev = ss.ring_s[l][1 - par];
@@ -880,21 +722,9 @@ static void mx_step_args(aec_crn_handle* h, const StreamState& ss, const Bufs& b
     ma.cst = ss.cst[l];
     ma.hx = ss.hx;
     ma.cnt = ss.mx_cnt;
-    ma.dst = reinterpret_cast<crn::bf16_t*>(last ? bf.cat[L] : xn_out);
-    ma.ldd = last ? 2 * ch[L] : (int64_t)S * Q;
-    ma.ldf = D * ma.ldd;
-    ma.dshift = ilog2(Q);
+    ma.dst = reinterpret_cast<bf16_t*>(last ? bf.cat[L] : out_b ? ss.xnb : bf.xn);
     ma.q8 = last ? bf.cat8[L] : out_b ? ss.xn8b : bf.xn8;
     ma.qs = last ? bf.cats[L] : out_b ? ss.xnsb : bf.xns;
-    ma.B = B;
-    ma.H = H;
-}
-
-static aec_status run_lstm_mx_step(aec_crn_handle* h, StreamState& ss, const Bufs& bf, int l, int par, hipStream_t st) {
-    crn::StepMxArgs ma;
-    crn::RowSrc q;
-    mx_step_args(h, ss, bf, l, par, ma, &q);
-    if (q.src) CRN_TRY(h, crn::launch_mx8_quant(q, bf.aq, bf.as, st));
     CRN_TRY(h, crn::launch_lstm_step_mx8(ma, st));
     return AEC_OK;
 }
@@ -909,7 +739,10 @@ static hipError_t stream_cov_fill(aec_crn_handle* h, int first, int count, hipSt
                                        h->cfg.nlms_taps, h->kal_p0, st);
 }
 
-// the fused front's level table (stream_open checked the shapes: stream_enc_levels)
+// the fused front's level table (stream_open checked the shapes: stream_enc_levels).  Its levels
+// take enc_level's shadow rule as the batch front's do; for every table stream_enc_levels admits
+// that rule is shadow_level alone: levels 0-2 are admitted only without a shadow, and level 3's
+// 128 bf16 columns always suit one (shadow_cols)
 static crn::StreamEncArgs stream_enc_args(aec_crn_handle* h, int B) {
     StreamState& ss = *h->ss;
     const int* ch = h->cfg.conv_channels;
@@ -932,52 +765,21 @@ static crn::StreamEncArgs stream_enc_args(aec_crn_handle* h, int B) {
         ea.mx4.wsc = pk.wsc;
         ea.mx4.bias = pk.bias;
         ea.mx4.alpha = pk.alpha;
-        ea.mx4.out = reinterpret_cast<bf16_t*>(ss.cat[5]);
+        ea.mx4.out = reinterpret_cast<bf16_t*>(ss.fb.cat[5]);
         ea.mx4.ldo = 2 * ch[5];
         ea.mx4.choff = ch[5];
-        ea.mx4.q8 = ss.cat8[5];
-        ea.mx4.qs = ss.cats[5];
+        ea.mx4.q8 = ss.fb.cat8[5];
+        ea.mx4.qs = ss.fb.cats[5];
     }
-    for (int i = 0; i < ss.enc_nlev; ++i) {
-        const Packed& pk = h->enc[i];
-        crn::StreamEncLevel& L = ea.lev[i];
-        L.w = reinterpret_cast<const bf16_t*>(pk.w);
-        L.bias = pk.bias;
-        L.alpha = pk.alpha;
-        L.kpad = pk.kpad;
-        L.N = pk.N;
-        L.nchunk = (pk.K + 31) / 32;
-        L.cin_shift = ilog2(i == 0 ? 8 : ch[i]);
-        L.out = reinterpret_cast<bf16_t*>(ss.cat[i + 1]);
-        L.ldo = 2 * ch[i + 1];
-        L.choff = ch[i + 1];
-        if (shadow_level(*h, i + 1)) {
-            L.q8 = ss.cat8[i + 1];
-            L.qs = ss.cats[i + 1];
-        }
-    }
+    for (int i = 0; i < ss.enc_nlev; ++i) ea.lev[i] = enc_level(h, ss.fb, i);
     return ea;
 }
 
 // the fused back's level table: decoder levels cl = 3, 2, 1 (decf[L - 3 .. L - 1])
 static crn::StreamDecArgs stream_dec_args(aec_crn_handle* h, int B) {
     StreamState& ss = *h->ss;
-    const int* ch = h->cfg.conv_channels;
     crn::StreamDecArgs da{};
-    for (int l = 0; l < 3; ++l) {
-        const int cl = 3 - l, d = h->L - cl;
-        const Packed& pk = h->decf[d];
-        crn::StreamDecLevel& L = da.lev[l];
-        L.w = reinterpret_cast<const bf16_t*>(pk.w);
-        L.bias = pk.bias;
-        L.alpha = pk.alpha;
-        L.act = pk.act;
-        L.kpad = pk.kpad;
-        L.N = pk.N;
-        L.nchunk = (pk.K + 31) / 32;
-        L.cin_shift = ilog2(2 * ch[cl]);
-        L.src = reinterpret_cast<const bf16_t*>(ss.cat[cl]);
-    }
+    for (int l = 0; l < 3; ++l) da.lev[l] = dec_level(h, ss.fb, 3 - l);
     da.tab = h->d_tab;
     da.espec = h->cfg.nlms_taps > 0 ? ss.espec : nullptr;
     da.tail = ss.tail;
@@ -985,96 +787,16 @@ static crn::StreamDecArgs stream_dec_args(aec_crn_handle* h, int B) {
     return da;
 }
 
-// the last three decoder levels crn_stream_dec_kernel can take (fused-parity bf16 GEMMs, the
-// map shapes of configs.net_conf's narrow levels)
-static bool stream_dec_ok(const aec_crn_handle* h) {
-    if (h->es != 2 || h->L < 3) return false;
-    // AEC_CRN_STREAM_FUSE (A/B knob; unset = every bit on, i.e. 31): bit 0 fused front (encoder
-    // levels 0-2), bit 1 fused back (decoder cl = 3..1 + mask + irFFT), bit 2 encoder level 3 in the
-    // front, bit 3 decoder cl = 4 (MX) in the back, bit 4 encoder level 4 (MX) in the front; the MX
-    // folds (bits 3, 4) are further limited to streams <= CUs at stream_open
-    if (!(AEC_MODE_KNOB("AEC_CRN_STREAM_FUSE", 31) & 2)) return false;
-    const int* ch = h->cfg.conv_channels;
-    const int caps[3] = {crn::kStreamDecChunks0, crn::kStreamDecChunks1, crn::kStreamDecChunks2};
-    for (int l = 0; l < 3; ++l) {
-        const int cl = 3 - l, d = h->L - cl, Fin = 256 >> cl;
-        const Packed& pk = h->decf[d];
-        const int NT = (pk.N + 15) / 16;
-        if (!pk.w || pk.wq || (pk.K + 31) / 32 != caps[l] || pk.kpad < 32 * ((pk.K + 31) / 32) || (Fin / 16) * NT != 8 ||
-            4 % NT || Fin * 2 * ch[cl] > 4096 || ilog2(2 * ch[cl]) != 7 - l)
-            return false;
-        if (l < 2 && (pk.act != 1 || pk.N != 2 * ch[cl - 1] || pk.N % 32)) return false;
-        if (l == 2 && (pk.N != 4 || pk.act == 1)) return false;
-    }
-    return true;
-}
-
-// decoder cl = 4 inside the fused back (MX-fp8 step, AEC_CRN_STREAM_FUSE bit 3, default on): its
-// fused-parity MX GEMM at net_conf's shape (16 input bins x 256 channels -> 2 x 64 columns, K = 768)
-// reading cat[4]'s shadow, split into 1 or 2 K slices
-static bool stream_dec_mx_ok(const aec_crn_handle* h) {
-    if (!(AEC_MODE_KNOB("AEC_CRN_STREAM_FUSE", 31) & 8)) return false;
-    if (h->L < 5 || !h->ss) return false;
-    const int* ch = h->cfg.conv_channels;
-    const Packed& pk = h->decf[h->L - 4];
-    const int ks = conv_ksplit(pk.kpad);
-    return pk.wq && pk.wsc && pk.act == 1 && pk.N == 128 && pk.K == 768 && pk.kpad == 768 && ch[4] == 128 &&
-           ch[3] == 64 && shadow_level(*h, 4) && h->ss->cat8.size() > 4 && h->ss->cat8[4] && h->ss->cats[4] && (ks == 1 || ks == 2);
-}
-
-// encoder level 4 inside the fused front (MX-fp8 step, AEC_CRN_STREAM_FUSE bit 4, default on): its
-// MX GEMM at net_conf's shape (8 output bins x 256 channels, K = 5 taps x 128, one K slice) on level
-// 3's shadow, its output with a shadow for level 5
-static bool stream_enc_mx_ok(const aec_crn_handle* h) {
-    if (!(AEC_MODE_KNOB("AEC_CRN_STREAM_FUSE", 31) & 16)) return false;
-    if (h->L < 6 || !h->ss) return false;
-    if (h->kalman && h->cfg.nlms_taps > 0 && !crn::stream_enc_kalman_ok(h->cfg.nlms_taps, true)) return false;
-    const int* ch = h->cfg.conv_channels;
-    const Packed& pk = h->enc[4];
-    const StreamState& ss = *h->ss;
-    return pk.wq && pk.wsc && pk.act == 1 && pk.N == 256 && pk.K == 640 && pk.kpad == 640 && ch[4] == 128 &&
-           ch[5] == 256 && conv_ksplit(pk.kpad) == 1 && ss.cat8.size() > 5 && ss.cat8[4] && ss.cats[4] &&
-           ss.cat8[5] && ss.cats[5];
-}
-
-// leading encoder levels crn_stream_enc_kernel can take: bf16 GEMM (not MX), PReLU, 8 output tiles
-// of 16 bins x 16 channels, K <= 160, no MX shadow on the output
-static int stream_enc_levels(const aec_crn_handle* h) {
-    if (h->es != 2) return 0;
-    const int fuse = AEC_MODE_KNOB("AEC_CRN_STREAM_FUSE", 31);
-    if (!(fuse & 1)) return 0;
-    // a Kalman fused front that is not built (it would spill): the separate launches
-    if (h->kalman && h->cfg.nlms_taps > 0 && !crn::stream_enc_kalman_ok(h->cfg.nlms_taps, false)) return 0;
-    const int* ch = h->cfg.conv_channels;
-    int n = 0;
-    // levels 0-2 together, at net_conf's shapes (crn_stream_enc_kernel's compile-time chunk counts)
-    const int nc[3] = {2, 3, 5};
-    for (int i = 0; i < std::min(3, h->L); ++i) {
-        const Packed& pk = h->enc[i];
-        const int cin = i == 0 ? 8 : ch[i];
-        if (pk.wq || pk.act != 1 || pk.N != (16 << i) || cin != (8 << i) || (pk.K + 31) / 32 != nc[i] ||
-            pk.kpad < 32 * nc[i] || shadow_level(*h, i + 1))
-            return 0;
-        ++n;
-    }
-    if (n < 3) return 0;
-    // level 3 (16 x 128 from the 32 x 64 map; its MX shadow written in the kernel): AEC_CRN_STREAM_FUSE bit 2
-    if (n == 3 && h->L > 4 && (fuse & 4)) {
-        const Packed& pk = h->enc[3];
-        const int nc = (pk.K + 31) / 32;
-        if (!pk.wq && pk.act == 1 && pk.N == 128 && ch[3] == 64 && ch[4] == 128 && nc == crn::kStreamEncChunks3 &&
-            pk.kpad >= 32 * nc)
-            ++n;
-    }
-    return n;
+// a Kalman fused front that is not built (it would spill) takes the separate launches
+static bool kalman_front_built(const aec_crn_handle* h, bool mx4) {
+    return !(h->kalman && h->cfg.nlms_taps > 0 && !crn::stream_enc_kalman_ok(h->cfg.nlms_taps, mx4));
 }
 
 template <typename T>
 static aec_status stream_launches(aec_crn_handle* h, int par, const StreamIo& io, hipStream_t st) {
     StreamState& ss = *h->ss;
     const int B = ss.B;
-    const Bufs bf{ss.x0,       ss.cat.data(), ss.gx,   ss.xn,  ss.mask,     ss.aq,    ss.as, ss.cat8.data(),
-                  ss.cats.data(), ss.xn8,      ss.xns, ss.skp, ss.skc, ss.sk_bytes, ss.skc_n};
+    const FeatureBufs& bf = ss.fb;
     float* cur_mic = ss.hop + (size_t)(par * 2 + 0) * B * 256;
     float* cur_far = ss.hop + (size_t)(par * 2 + 1) * B * 256;
     const float* prev_mic = ss.hop + (size_t)((1 - par) * 2 + 0) * B * 256;
@@ -1099,7 +821,7 @@ static aec_status stream_launches(aec_crn_handle* h, int par, const StreamIo& io
         static const bool rerun = AEC_AB_KNOB("AEC_CRN_ENC_MX_RERUN", 0) != 0;
         first = ss.enc_nlev + (ss.enc_mx && !rerun ? 1 : 0);
     } else {
-        crn::StreamFrontArgs fa{prev_mic, io.mic, prev_far, io.far, h->d_tab, ss.x0, B};
+        crn::StreamFrontArgs fa{prev_mic, io.mic, prev_far, io.far, h->d_tab, bf.x0, B};
         fa.ld_cur = io.ld_in;
         fa.save_mic = cur_mic;
         fa.save_far = cur_far;
@@ -1108,7 +830,7 @@ static aec_status stream_launches(aec_crn_handle* h, int par, const StreamIo& io
         ss.front_node[par] = last_node(st);
         ss.front_args[par] = fa;
         if (c.nlms_taps > 0) {
-            crn::StreamNlmsArgs na{ss.nrows, ss.nstate, ss.espec, ss.x0, B, c.nlms_mu, c.nlms_beta, c.nlms_delta};
+            crn::StreamNlmsArgs na{ss.nrows, ss.nstate, ss.espec, bf.x0, B, c.nlms_mu, c.nlms_beta, c.nlms_delta};
             if (h->kalman) {
                 crn::StreamKalmanArgs ka{na, h->kal_p0};
                 ka.mu = h->kal_a;
@@ -1118,30 +840,30 @@ static aec_status stream_launches(aec_crn_handle* h, int par, const StreamIo& io
             }
         }
     }
-    aec_status s = run_encoder<T>(h, bf, B, st, first);
+    aec_status s = run_encoder<T>(h, bf, B, st, first, false, &ss.sk);
     if (s != AEC_OK) return s;
     for (int l = 0; l < h->nrnn; ++l) {
         if (ss.mx_step) {
             if constexpr (sizeof(T) == 2) {
-                s = run_lstm_mx_step(h, ss, bf, l, par, st);
+                s = run_lstm_mx_step(h, ss, l, par, st);
                 if (s != AEC_OK) return s;
             }
             continue;
         }
         s = run_lstm_input<T>(h, bf, l, B, st);
         if (s != AEC_OK) return s;
-        crn::StepArgs sa{h->lhh[l].w, ss.gx, ss.ring_y[l][1 - par], ss.ring_y[l][par], ss.cst[l], B, h->H, 0, 0};
+        crn::StepArgs sa{h->lhh[l].w, bf.gx, ss.ring_y[l][1 - par], ss.ring_y[l][par], ss.cst[l], B, h->H, 0, 0};
         CRN_TRY(h, crn::launch_lstm_step<T>(sa, h->CELLS, h->S, st));
         s = run_lstm_combine<T>(h, bf, l, ss.ring_y[l][par], B, st);
         if (s != AEC_OK) return s;
     }
     if (ss.dec_fused) {
-        s = run_decoder<T>(h, bf, B, st, h->L - (ss.dec_mx ? 4 : 3));
+        s = run_decoder<T>(h, bf, B, st, h->L - (ss.dec_mx ? 4 : 3), 0, &ss.sk);
         if (s != AEC_OK) return s;
         crn::StreamDecArgs da = stream_dec_args(h, B);
         if (ss.dec_mx) {
             const Packed& pk = h->decf[h->L - 4];
-            da.mx = crn::StreamDecMxLevel{pk.wq, pk.wsc, pk.bias, pk.alpha, ss.cat8[4], ss.cats[4], conv_ksplit(pk.kpad)};
+            da.mx = crn::StreamDecMxLevel{pk.wq, pk.wsc, pk.bias, pk.alpha, bf.cat8[4], bf.cats[4], conv_ksplit(pk.kpad)};
         }
         da.prev_mic = prev_mic;
         da.cur_mic = cur_mic;
@@ -1152,9 +874,9 @@ static aec_status stream_launches(aec_crn_handle* h, int par, const StreamIo& io
         ss.dec_args[par] = da;
         return AEC_OK;
     }
-    s = run_decoder<T>(h, bf, B, st);
+    s = run_decoder<T>(h, bf, B, st, -1, 0, &ss.sk);
     if (s != AEC_OK) return s;
-    crn::StreamBackArgs ba{prev_mic, cur_mic, h->d_tab, reinterpret_cast<const float2*>(ss.mask), ss.tail, io.out, B};
+    crn::StreamBackArgs ba{prev_mic, cur_mic, h->d_tab, reinterpret_cast<const float2*>(bf.mask), ss.tail, io.out, B};
     ba.ld_out = io.ld_out;
     if (c.nlms_taps > 0) ba.espec = ss.espec;
     CRN_TRY(h, crn::launch_stream_back(ba, mask_mode(h), st));
@@ -1375,99 +1097,67 @@ aec_status aec_crn_stream_open(aec_crn_handle* h, int32_t B) {
     ss.B = B;
     const size_t es = h->es;
     const int C = h->CELLS, S = h->S, H = h->H;
-    auto alloc = [&](auto** p, size_t bytes) {     // 0 bytes: the network has no such buffer
-        if (bytes == 0) return hipSuccess;
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(bytes, 16));
-        if (e == hipSuccess) {
-            ss.allocs.push_back(*p);
-            e = hipMemset(*p, 0, std::max<size_t>(bytes, 16));
-        }
-        return e;
-    };
-    const WsBytes wb = ws_bytes(*h, B, 1);         // the feature buffers of one frame per stream
-    CRN_TRY(h, alloc(&ss.x0, wb.x0));
-    ss.cat.assign(h->L + 1, nullptr);
-    for (int l = 1; l <= h->L; ++l) CRN_TRY(h, alloc(&ss.cat[l], wb.cat[l]));
-    CRN_TRY(h, alloc(&ss.gx, wb.gx));
-    CRN_TRY(h, alloc(&ss.xn, wb.xn));
-    CRN_TRY(h, alloc(&ss.aq, wb.aq));
-    CRN_TRY(h, alloc(&ss.as, wb.as));
-    ss.cat8.assign(h->L + 1, nullptr);
-    ss.cats.assign(h->L + 1, nullptr);
-    for (int l = 1; l <= h->L; ++l) {
-        CRN_TRY(h, alloc(&ss.cat8[l], wb.cat8[l]));
-        CRN_TRY(h, alloc(&ss.cats[l], wb.cats[l]));
-    }
-    CRN_TRY(h, alloc(&ss.xn8, wb.xn8));
-    CRN_TRY(h, alloc(&ss.xns, wb.xns));
-    CRN_TRY(h, alloc(&ss.mask, wb.mask));
+    auto alloc = [&](auto** p, size_t bytes) { return dev_alloc(p, bytes, ss.allocs, true); };   // zero-filled
+    // the feature buffers of one frame per stream
+    const aec_status fs = alloc_features(h, ss.fb, ws_bytes(*h, B, 1), ss.allocs, true);
+    if (fs != AEC_OK) return fs;
     if (h->mx8) {
         int64_t skb = 0, skt = 0;
         splitk_need(*h, B, &skb, &skt);
         if (skb > 0 && skt <= INT32_MAX) {
-            CRN_TRY(h, alloc(reinterpret_cast<void**>(&ss.skp), (size_t)skb));
-            CRN_TRY(h, alloc(reinterpret_cast<void**>(&ss.skc), (size_t)skt * sizeof(int)));   // zeroed
-            ss.sk_bytes = skb;
-            ss.skc_n = (int32_t)skt;
+            CRN_TRY(h, alloc(&ss.sk.skp, (size_t)skb));
+            CRN_TRY(h, alloc(&ss.sk.skc, (size_t)skt * sizeof(int)));   // zeroed
+            ss.sk.sk_bytes = skb;
+            ss.sk.skc_n = (int32_t)skt;
         }
     }
-    // dtype 2, NavieComplexLSTM: the recurrence runs as lstm_step_mx8_kernel (AEC_CRN_STEP_MX=0: the bf16
-    // step + combine, A/B only)
-    const int step_mx = AEC_MODE_KNOB("AEC_CRN_STEP_MX", 1);
-    ss.mx_step = step_mx != 0 && h->mx8 && C * S == 4 && h->nrnn > 0 && h->lcat[0].wq != nullptr;
+    // dtype 2, NavieComplexLSTM: the recurrence runs as lstm_step_mx8_kernel where every layer fits it;
+    // configs that pass the create-time checks but not its layout preconditions keep the bf16 step + combine
+    ss.mx_step = mx_step_ok(*h, AEC_MODE_KNOB("AEC_CRN_STEP_MX", 1), B);
     if (ss.mx_step && h->nrnn > 2) {
         CRN_TRY(h, alloc(&ss.xnb, (size_t)B * S * H * es));
         if (shadow_xn(*h)) {
-            CRN_TRY(h, alloc(reinterpret_cast<void**>(&ss.xn8b), (size_t)B * S * H));
-            CRN_TRY(h, alloc(reinterpret_cast<void**>(&ss.xnsb), (size_t)B * S * H / 32));
+            CRN_TRY(h, alloc(&ss.xn8b, (size_t)B * S * H));
+            CRN_TRY(h, alloc(&ss.xnsb, (size_t)B * S * H / 32));
         }
     }
     if (ss.mx_step) {
-        // the kernel's layout preconditions for every layer (x taps of >= 256 k, ...): configs that
-        // pass the create-time checks but not these keep the bf16 step + combine
-        const Bufs bf{ss.x0,       ss.cat.data(), ss.gx,   ss.xn,  ss.mask,     ss.aq,    ss.as, ss.cat8.data(),
-                      ss.cats.data(), ss.xn8,      ss.xns, ss.skp, ss.skc, ss.sk_bytes, ss.skc_n};
-        for (int l = 0; l < h->nrnn && ss.mx_step; ++l) {
-            crn::StepMxArgs ma;
-            mx_step_args(h, ss, bf, l, 0, ma, nullptr);
-            ss.mx_step = crn::lstm_step_mx8_layout_ok(ma) && h->lcat[l].wq != nullptr;
-        }
-    }
-    if (ss.mx_step) {
-        CRN_TRY(h, alloc(reinterpret_cast<void**>(&ss.hx), (size_t)B * C * S * H * sizeof(float)));
-        CRN_TRY(h, alloc(reinterpret_cast<void**>(&ss.mx_cnt), (size_t)crn::lstm_step_mx8_counters(H, B) * sizeof(int)));
+        CRN_TRY(h, alloc(&ss.hx, (size_t)B * C * S * H * sizeof(float)));
+        CRN_TRY(h, alloc(&ss.mx_cnt, (size_t)crn::lstm_step_mx8_counters(H, B) * sizeof(int)));
     }
     for (int l = 0; l < h->nrnn; ++l) {
         if (ss.mx_step) {
             for (int r = 0; r < 2; ++r) {
-                CRN_TRY(h, alloc(reinterpret_cast<void**>(&ss.ring_q[l][r]), (size_t)B * C * S * H));
-                CRN_TRY(h, alloc(reinterpret_cast<void**>(&ss.ring_s[l][r]), (size_t)B * C * S * H / 32));
+                CRN_TRY(h, alloc(&ss.ring_q[l][r], (size_t)B * C * S * H));
+                CRN_TRY(h, alloc(&ss.ring_s[l][r], (size_t)B * C * S * H / 32));
             }
         } else {
             CRN_TRY(h, alloc(&ss.ring_y[l][0], (size_t)B * C * S * H * es));
             CRN_TRY(h, alloc(&ss.ring_y[l][1], (size_t)B * C * S * H * es));
         }
-        CRN_TRY(h, alloc(reinterpret_cast<void**>(&ss.cst[l]), (size_t)B * C * S * H * sizeof(float)));
+        CRN_TRY(h, alloc(&ss.cst[l], (size_t)B * C * S * H * sizeof(float)));
     }
-    CRN_TRY(h, alloc(reinterpret_cast<void**>(&ss.hop), (size_t)4 * B * 256 * sizeof(float)));
-    CRN_TRY(h, alloc(reinterpret_cast<void**>(&ss.tail), (size_t)B * 256 * sizeof(float)));
+    CRN_TRY(h, alloc(&ss.hop, (size_t)4 * B * 256 * sizeof(float)));
+    CRN_TRY(h, alloc(&ss.tail, (size_t)B * 256 * sizeof(float)));
     if (h->cfg.nlms_taps > 0) {
-        CRN_TRY(h, alloc(reinterpret_cast<void**>(&ss.nrows), (size_t)B * 512 * sizeof(float2)));
+        CRN_TRY(h, alloc(&ss.nrows, (size_t)B * 512 * sizeof(float2)));
         const CancellerRows cr = crn_canceller_state_rows(h->cfg.nlms_taps, h->kalman != 0);
-        CRN_TRY(h, alloc(reinterpret_cast<void**>(&ss.nstate), (size_t)B * cr.bytes()));
+        CRN_TRY(h, alloc(&ss.nstate, (size_t)B * cr.bytes()));
         if (h->kalman) CRN_TRY(h, stream_cov_fill(h, 0, B, nullptr));
-        CRN_TRY(h, alloc(reinterpret_cast<void**>(&ss.espec), (size_t)B * 256 * sizeof(float2)));
+        CRN_TRY(h, alloc(&ss.espec, (size_t)B * 256 * sizeof(float2)));
     }
-    ss.enc_nlev = stream_enc_levels(h);
-    ss.dec_fused = stream_dec_ok(h);
+    // which fused kernels this handle's shapes admit (crn_plan.h), by AEC_CRN_STREAM_FUSE's bits
+    const int fuse = AEC_MODE_KNOB("AEC_CRN_STREAM_FUSE", kFuseAll);
+    ss.enc_nlev = kalman_front_built(h, false) ? stream_enc_levels(*h, fuse) : 0;
+    ss.dec_fused = stream_dec_ok(*h, fuse);
     // the MX folds (one block per stream, 1 wave per SIMD) win while every stream has a CU of its own;
     // past that the unfolded kernels' occupancy (2-3 waves per SIMD) wins: 4,096 streams 4.08 M vs
     // 3.35 M frames/s with both folds, 256 streams 0.1134 vs 0.1204 ms per hop (profiles/r04v_c5_fold_sweep.txt)
     int ncu = 256;
     CRN_TRY(h, hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device));
     const bool fold = B <= ncu;
-    ss.dec_mx = fold && ss.dec_fused && stream_dec_mx_ok(h);
-    ss.enc_mx = fold && ss.enc_nlev == 4 && stream_enc_mx_ok(h);
+    ss.dec_mx = fold && ss.dec_fused && stream_dec_mx_ok(*h, fuse);
+    ss.enc_mx = fold && ss.enc_nlev == 4 && kalman_front_built(h, true) && stream_enc_mx_ok(*h, fuse);
     CRN_TRY(h, hipStreamCreateWithFlags(&ss.cap, hipStreamNonBlocking));
     CRN_TRY(h, hipDeviceSynchronize());
     ss.k = 0;

@@ -22,11 +22,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "crn_host.h"
+#include "crn_plan.h"
 
 namespace crn {
 
-typedef uint16_t bf16_t;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -111,24 +110,7 @@ __device__ __forceinline__ float2 apply_mask(float2 x, float2 mk) {
 
 constexpr int kRowStride = 144;    // LDS bytes per staged row: 16 rows at one column hit 16 distinct 16-B bank slots
 
-// Implicit-GEMM row source shared by the conv, LSTM-input and dense loaders:
-//   row m -> (hi = m >> rshift, lo = m & (2^rshift - 1))
-//   k     -> (tap = k >> kshift, ci = k & (2^kshift - 1))
-//   element offset = hi*rs_hi + lo*rs_lo + tap*ks + ci + base_off
-//   valid iff m < M, k < K and 0 <= lo*pmul + tap + padd < plim  (zero otherwise:
-//   the conv's frequency padding and the K / M tails).
-struct RowSrc {
-    const void* src;
-    int64_t M;
-    int32_t K;
-    int32_t rshift;
-    int64_t rs_hi, rs_lo;
-    int32_t kshift;
-    int32_t pmul, padd, plim;
-    int64_t ks, base_off;
-    int64_t src_elems;          // elements of the source tensor (buffer range of the DMA path)
-};
-
+// one 16-byte chunk of an implicit-GEMM row (RowSrc: crn_plan.h)
 template <typename T>
 __device__ __forceinline__ u32x4 rowsrc_load(const RowSrc& a, int64_t m, int kbyte) {
     constexpr int E = Elem<T>::kPer16;

@@ -7,7 +7,9 @@
 // conversions, the per-layer rules (MX-fp8 GEMM, fused decoder levels, MX
 // shadows) and the workspace sizes.  Plain C++17 with no HIP in it, so a host
 // compiler builds it alone and tests/host/crn_host_check.cpp runs it under the
-// CPU sanitizers; crn_api.hip allocates, copies and launches.
+// CPU sanitizers; crn_api.hip allocates, copies and launches.  What the
+// forward pass does with these shapes (each launch's geometry, which kernel a
+// config gets) is crn_plan.h, built on this header under the same rule.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

@@ -61,42 +61,7 @@ struct BackArgs {
     int32_t dm_kpad = 0, dm_cin_shift = 0, dm_act = 0;
 };
 
-// Row-GEMM epilogue: out[(m >> oshift)*o_hi + (m & mask)*o_lo + o_add + n] =
-// act(acc + bias[n]) for m < M, n < N; act 0 none, 1 PReLU(alpha), 2 tanh.
-struct RowEpi {
-    void* out;
-    int64_t M;
-    int32_t N;
-    int32_t oshift;
-    int64_t o_hi, o_lo, o_add;
-    const float* bias;
-    float alpha;
-    int32_t act;
-    int32_t mode = 0;           // timing experiments only (CRN_GEMM_MODE): bit0 skip the epilogue
-    // tile order (speed only, never the result): 0 = row tiles in order, column tiles fastest;
-    // g > 0 = XCD-aware: each set of blocks sharing an XCD gets a contiguous range of tile ids,
-    // walked g row tiles per column step (crn_gemm.h tile_order)
-    int32_t xcd_gm = 0;
-    // column split (the decoder's fused parities): columns n >= nsplit are
-    // stored at element offset split_add + (n - nsplit) instead of n
-    int32_t nsplit = 0x7fffffff;
-    int64_t split_add = 0;
-    // MX-fp8 shadow of the output (bf16 outputs, N % 32 == 0): e4m3 bytes at the output's element
-    // offsets (q8) and one E8M0 scale per 32-column group at element offset / 32 (qs), the
-    // operand an MX GEMM consumer reads in place (launch_gemm_mx8_rows); null: none
-    uint8_t* q8 = nullptr;
-    uint8_t* qs = nullptr;
-    // split-K (launch_gemm_mx8*): ksplit > 1 runs the 64 x 64 tile grid ksplit times over K
-    // slices; skp holds the f32 partial tiles (sk_bytes >= mx8_splitk_bytes), skc one arrival
-    // counter per output tile (skc_n >= mx8_splitk_tiles ints, zero between launches).  The
-    // caller picks ksplit per layer (never from M), so a row's result does not depend on the
-    // batch it sits in.
-    int32_t ksplit = 1;
-    int32_t skc_n = 0;
-    float* skp = nullptr;
-    int* skc = nullptr;
-    int64_t sk_bytes = 0;
-};
+// RowSrc / RowEpi, the row GEMMs' geometry: crn_plan.h
 
 // One LSTM frame step for CELLS weight sets x S input sequences (v1: 1x1,
 // v2 NavieComplexLSTM: 2x2), gate columns packed per 16 units (i|f|g|o).
@@ -112,36 +77,9 @@ struct StepArgs {
     int32_t mode;               // timing experiments only (CRN_STEP_MODE)
 };
 
-// MX-fp8 layer step of a NavieComplexLSTM (CELLS = S = 2): input projection,
-// recurrence, cell update and combination in one launch (lstm_step_mx8_kernel),
-// the per-hop streaming form.
-struct StepMxArgs {
-    const uint8_t* wq;          // [W_ih | W_hh] e4m3 [2*4H][2H] in W_hh's packed row order (pack_lstm),
-    const uint8_t* wsc;         //   E8M0 per 32 k [2*4H][2H/32]
-    const float* bias;          // b_ih + b_hh [2][H][4] (a unit's 4 gates adjacent)
-    const uint8_t* xq;          // layer input x as e4m3: element (b, s, k) at
-    const uint8_t* xs;          //   b*x_f + s*x_s + (k >> x_sh)*x_t + (k & (2^x_sh - 1)) + x_0 (2^x_sh % 256 == 0);
-    int64_t x_f, x_s, x_t, x_0, x_elems;   //   its E8M0 per 32 k at element offset / 32
-    int32_t x_sh;
-    const uint8_t* hq_prev;     // h_{t-1} e4m3 [B][2][2][H], E8M0 per 32 units: hs_prev [B][2][2][H/32]
-    const uint8_t* hs_prev;
-    uint8_t* hq_cur;            // h_t, same layout
-    uint8_t* hs_cur;
-    float* cst;                 // c [B][2][2][H] (read, written)
-    float* hx;                  // h_t f32 [B][2][2][H]: the cell pair's hand-off
-    int* cnt;                   // lstm_step_mx8_counters(H, B) arrival counters, zero between launches
-    bf16_t* dst;                // combined rows: real at b*ldf + (j >> dshift)*ldd + (j & (2^dshift - 1)),
-    int64_t ldf, ldd;           //   imag at + 2^dshift (lstm_combine_kernel's map)
-    int32_t dshift;
-    uint8_t* q8;                // their MX-fp8 shadow (RowEpi::q8 layout), nullable
-    uint8_t* qs;
-    int32_t B, H;
-    int32_t mode = 0;           // timing experiments only (CRN_MX_STEP_MODE; results invalid unless 0)
-};
+// MX-fp8 layer step of a NavieComplexLSTM (lstm_step_mx8_kernel): StepMxArgs and its layout
+// preconditions lstm_step_mx8_layout_ok are in crn_plan.h
 hipError_t launch_lstm_step_mx8(const StepMxArgs& a, hipStream_t st);
-// the layout preconditions of lstm_step_mx8_kernel (H % 256, 128-k stages inside one x tap, 32-unit
-// output groups): the pointer-free part of launch_lstm_step_mx8's argument check
-bool lstm_step_mx8_layout_ok(const StepMxArgs& a);
 int64_t lstm_step_mx8_counters(int H, int B);
 
 // Streaming (one hop per stream): frame = [prev hop, cur hop] of each stream
@@ -191,24 +129,10 @@ struct StreamBackArgs {
 // Fused per-hop front (crn_stream.hip): frame -> rFFT of mic and far -> [FD-NLMS step] -> X0 ->
 // encoder levels 0 .. nlev-1 (bf16 implicit-GEMM MFMA, 8 tiles of 16 x 16 per level), one block
 // per stream; replaces launch_stream_front + launch_stream_nlms + those levels' row GEMMs.
-constexpr int kStreamEncChunks = 5;   // 32-k chunks per level 0-2 (K <= 160)
-constexpr int kStreamEncChunks3 = 10; // level 3 (K <= 320)
-struct StreamEncLevel {
-    const bf16_t* w;            // packed [npad][kpad] (pack_encoder)
-    const float* bias;
-    float alpha;                // PReLU
-    int32_t kpad, N, nchunk;    // nchunk = ceil(K / 32)
-    int32_t cin_shift;          // log2 of the input map's channels per bin (3: X0's 8)
-    bf16_t* out;                // cat[l + 1] [B][Fo][ldo]: the encoder half at channel offset choff
-    int64_t ldo;
-    int32_t choff;
-    uint8_t* q8 = nullptr;      // level 3: the output's MX-fp8 shadow (RowEpi::q8 / qs layout) or null
-    uint8_t* qs = nullptr;
-};
+// (StreamEncLevel and the chunk / stage counts: crn_plan.h)
 // Optional last level of the fused front (fp8 step, AEC_CRN_STREAM_FUSE bit 4): encoder level 4
 // as its MX-fp8 GEMM (scaled MFMA, 8 output bins x 256 channels, K = 5 taps x 128) on level 3's
 // e4m3 shadow kept in LDS; its output (and the output's MX-fp8 shadow) -> cat[5]'s encoder half.
-constexpr int kStreamEncMxStages = 5;   // 128-k stages of level 4 (K = 640)
 struct StreamEncMxLevel {
     const uint8_t* wq = nullptr;  // [npad8][640] e4m3
     const uint8_t* wsc = nullptr; // [npad8][20] E8M0
@@ -266,21 +190,11 @@ hipError_t launch_enc_batch(const EncBatchArgs& a, hipStream_t st);
 // + launch_stream_back.  Level i's input map = [decoder half | encoder half] of cat[cl]; the
 // first map comes whole from HBM, the later ones take the previous level's output as decoder
 // half and the encoder half from HBM.
-constexpr int kStreamDecChunks0 = 12, kStreamDecChunks1 = 6, kStreamDecChunks2 = 3;   // K <= 384 / 192 / 96
-struct StreamDecLevel {
-    const bf16_t* w;            // packed [npad][kpad] (pack_decoder_fused: columns [0, Co) parity 0, [Co, 2 Co) parity 1)
-    const float* bias;
-    float alpha;
-    int32_t act;                // 1 PReLU (levels), 0 none / 2 tanh (the mask level)
-    int32_t kpad, N, nchunk;    // N = 2 Co (4 at the mask level)
-    int32_t cin_shift;          // log2 of the input map's channels per bin (2 ch[cl])
-    const bf16_t* src;          // cat[cl] [B][Fin][2 ch[cl]]: the whole map (level 0) or its encoder half (later levels)
-};
+// (StreamDecLevel and the chunk / stage counts: crn_plan.h)
 // Optional first level of the fused back (fp8 step, AEC_CRN_STREAM_FUSE bit 3): decoder cl = 4 as
 // its MX-fp8 GEMM (scaled MFMA on cat[4]'s e4m3 shadow and the e4m3 weights, 16 input bins x 128
 // columns = both parities of 64 channels, K = 3 taps x 256), its output cat[3]'s decoder half kept
 // in LDS.  The K slices (ksplit 1 or 2) summed as gemm_mx8_kernel's split-K reducer sums them.
-constexpr int kStreamMxStages = 6;   // 128-k stages of cl = 4 (K = 768)
 struct StreamDecMxLevel {
     const uint8_t* wq;          // [npad8][768] e4m3 (pack_decoder_fused order, MX)
     const uint8_t* wsc;         // [npad8][24] E8M0
