@@ -50,6 +50,12 @@
 #ifndef AEC_SPEC_LD_NT
 #define AEC_SPEC_LD_NT 0   // E-spectrum row loads nt (A/B builds only)
 #endif
+#ifndef AEC_SPEC_BUF
+// E-spectrum rows through raw buffer loads, slot 0 taken apart where the rows are used (0: global
+// loads, A/B builds).  Bit-identical; the tick 9.4 k -> 8.35 k cycles, the C2 step 0.504-0.506 ->
+// 0.496-0.498 ms (profiles/synth_role.txt)
+#define AEC_SPEC_BUF 1
+#endif
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -656,36 +662,88 @@ __global__ __launch_bounds__(64 * (NS + kHelperWaves), 1) void gru_synth_kernel(
             if (s == z) nhop = nhops[z], bq = bs[z];
         const int64_t sstride = y.spec_stride ? y.spec_stride : 256;
         const float2* spec = y.spec + (int64_t)bq * y.Tmax * sstride;
+        // The wave's four slots lie in one stream (4 divides TF): its first slot's frame of a chunk,
+        // the stream's rows and its last frame, wave-uniform and made provably so (the row
+        // descriptor stays in SGPRs).  readfirstlane returns int: each half goes through uint32_t,
+        // or a low half with bit 31 set sign-extends over the high half.
+        auto uniform64 = [](uint64_t v) {
+            const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
+            const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+            return (uint64_t)hi << 32 | lo;
+        };
+        const int fs0 = __builtin_amdgcn_readfirstlane(fs - gg);
+        const uint64_t spec_u = uniform64(reinterpret_cast<uint64_t>(spec));
+        const int64_t nhop_u = (int64_t)uniform64((uint64_t)nhop);
+        constexpr bool kRawRows = !PIPE && AEC_SPEC_BUF;       // xa / xb hold the rows as stored
         float2 xa[8] = {}, xb[8] = {}, x128 = {};
         auto load_rows = [&](int cc) {
             // E rows of chunk cc.  A frame past the last one (t > nhop) feeds no
             // written hop (hop j reads frames j and j + 1 <= nhop), so it may
             // read any valid row: the index is clamped, the loads stay plain
-            // global loads with no per-lane select.
-            const int64_t t = min((int64_t)cc * TF + fs, nhop);
-            const float2* row = spec + t * sstride;
+            // loads with no per-lane select.
+            if constexpr (kRawRows) {
+                // Raw buffer loads (wave_prefetch's form, aec_stft.h): one descriptor per wave and
+                // chunk, based at the wave's first (clamped) frame t0 and covering its <= 4 rows,
+                // and a 32-bit lane offset, where a global load takes a 64-bit address built per
+                // lane and load.  The rows arrive as stored: slot 0 = (E[0], E[256]) is taken
+                // apart where the rows are used (rows_in), so nothing here waits for a load and
+                // all 17 are in flight under the inverse transform.  With the slot taken apart
+                // here the compiler branched round lane 0's unused mirror load and waited for the
+                // first load to return before it issued the other 16: one memory latency per tick
+                // in the role that sets the tick.
+                const int64_t t0 = min((int64_t)cc * TF + fs0, nhop_u);
+                const int dt = (int)(min((int64_t)cc * TF + fs, nhop) - t0);             // 0..3
+                const int dtmax = (int)(min((int64_t)cc * TF + fs0 + 3, nhop_u) - t0);   // the wave's last row
+                const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+                    reinterpret_cast<void*>(spec_u + (uint64_t)(t0 * sstride) * 8), (short)0,
+                    (dtmax * (int)sstride + 256) * 8, 0x00020000);
+                const int base = dt * (int)sstride * 8;
+                auto ld = [&](int slot) {
+                    const auto w = __builtin_amdgcn_raw_buffer_load_b64(rs, base + slot * 8, 0, AEC_SPEC_LD_NT ? 2 : 0);
+                    return make_float2(__uint_as_float(w[0]), __uint_as_float(w[1]));
+                };
 #pragma unroll
-            for (int m = 0; m < 8; ++m) {
-                const int kk = lb + 16 * m;
+                for (int m = 0; m < 8; ++m) {
+                    const int kk = lb + 16 * m;
+                    xa[m] = ld(kk);
+                    xb[m] = ld((256 - kk) & 255);
+                }
+                x128 = ld(128);
+            } else {
+                const int64_t t = min((int64_t)cc * TF + fs, nhop);
+                const float2* row = spec + t * sstride;
+#pragma unroll
+                for (int m = 0; m < 8; ++m) {
+                    const int kk = lb + 16 * m;
 #if AEC_SPEC_LD_NT
-                if constexpr (PIPE) {
-                    const float2 a = ld_coherent2(row + kk), c2 = ld_coherent2(row + ((256 - kk) & 255));
+                    if constexpr (PIPE) {
+                        const float2 a = ld_coherent2(row + kk), c2 = ld_coherent2(row + ((256 - kk) & 255));
+                        xa[m] = kk == 0 ? make_float2(a.x, 0.f) : a;
+                        xb[m] = kk == 0 ? make_float2(a.y, 0.f) : c2;
+                        continue;
+                    }
+                    typedef float f2v __attribute__((ext_vector_type(2)));
+                    const f2v av = __builtin_nontemporal_load(reinterpret_cast<const f2v*>(row + kk));
+                    const f2v cv = __builtin_nontemporal_load(reinterpret_cast<const f2v*>(row + ((256 - kk) & 255)));
+                    const float2 a = make_float2(av.x, av.y), c2 = make_float2(cv.x, cv.y);
+#else
+                    const float2 a = PIPE ? ld_coherent2(row + kk) : row[kk];
+                    const float2 c2 = PIPE ? ld_coherent2(row + ((256 - kk) & 255)) : row[(256 - kk) & 255];
+#endif
                     xa[m] = kk == 0 ? make_float2(a.x, 0.f) : a;
                     xb[m] = kk == 0 ? make_float2(a.y, 0.f) : c2;
-                    continue;
                 }
-                typedef float f2v __attribute__((ext_vector_type(2)));
-                const f2v av = __builtin_nontemporal_load(reinterpret_cast<const f2v*>(row + kk));
-                const f2v cv = __builtin_nontemporal_load(reinterpret_cast<const f2v*>(row + ((256 - kk) & 255)));
-                const float2 a = make_float2(av.x, av.y), c2 = make_float2(cv.x, cv.y);
-#else
-                const float2 a = PIPE ? ld_coherent2(row + kk) : row[kk];
-                const float2 c2 = PIPE ? ld_coherent2(row + ((256 - kk) & 255)) : row[(256 - kk) & 255];
-#endif
-                xa[m] = kk == 0 ? make_float2(a.x, 0.f) : a;
-                xb[m] = kk == 0 ? make_float2(a.y, 0.f) : c2;
+                x128 = PIPE ? ld_coherent2(row + 128) : row[128];
             }
-            x128 = PIPE ? ld_coherent2(row + 128) : row[128];
+        };
+        // the rows as synth_pack takes them: slot 0 of a raw row -> (E[0], 0), (E[256], 0) on lane 0
+        auto rows_in = [&](float2 (&ya)[8], float2 (&yb)[8]) {
+#pragma unroll
+            for (int m = 0; m < 8; ++m) ya[m] = xa[m], yb[m] = xb[m];
+            if constexpr (kRawRows) {
+                ya[0] = lb == 0 ? make_float2(xa[0].x, 0.f) : xa[0];
+                yb[0] = lb == 0 ? make_float2(xa[0].y, 0.f) : xb[0];
+            }
         };
         for (int c = -3; c <= nchmax + 2; ++c) {
             GTICK(0);
@@ -697,7 +755,9 @@ __global__ __launch_bounds__(64 * (NS + kHelperWaves), 1) void gru_synth_kernel(
             if (cs >= 0 && cs < nchmax && !(y.fmode & 1)) {
                 float* scr = sOut + (cs & 1) * (kSynWaves * 4 * kGroupFloats) + fl * kGroupFloats;
                 float2 v[16];
-                synth_pack(xa, xb, x128, sEst + ((cs & 1) * kCH + fl) * kEstS, sBin, sTw512, lb, v);
+                float2 ya[8], yb[8];
+                rows_in(ya, yb);
+                synth_pack(ya, yb, x128, sEst + ((cs & 1) * kCH + fl) * kEstS, sBin, sTw512, lb, v);
                 if (next) {
                     wait_chunks(c);
                     load_rows(c - 1);
