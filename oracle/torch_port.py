@@ -42,7 +42,9 @@ class TorchPort:
         with torch.no_grad():
             for k in ['weight_ih_l0', 'weight_hh_l0', 'bias_ih_l0', 'bias_hh_l0']:
                 getattr(self.gru, k).copy_(torch.from_numpy(np.asarray(weights['gru1.' + k])))
-        g = lambda k: torch.from_numpy(np.asarray(weights[k], np.float32))
+        # a copy: TorchTrainPort's Adam updates these in place, and from_numpy
+        # alone would share (and so rewrite) the caller's arrays
+        g = lambda k: torch.from_numpy(np.array(weights[k], np.float32))
         self.w1, self.b1 = g('linear1.weight'), g('linear1.bias')
         self.w2, self.b2 = g('linear2.weight'), g('linear2.bias')
         self.eye = torch.eye(WIN)[:, None, :]

@@ -297,6 +297,21 @@ def test_torch_train_port_matches_reference(tg, golden_weights, golden_erb):
             assert _rel(p.grad.numpy(), tg[f'grad{it}/{k}']) <= 1e-4, (it, k)
 
 
+def test_torch_train_port_leaves_its_weights_alone(tg, golden_erb):
+    """The port's Adam step updates its own copy of the weights: the arrays it
+    was built from (the session's golden weights, for every later test) stay
+    as they were."""
+    import torch
+    from torch_port import TorchTrainPort
+    w = dict(np.load(os.path.join(GOLDEN, 'weights.npz')))
+    before = {k: v.copy() for k, v in w.items()}
+    port = TorchTrainPort(w, golden_erb.astype(np.float32), lr=LR)
+    port.step(*(torch.from_numpy(tg[f'{s}0']) for s in ('mic', 'ref', 'near')))
+    for k in PARAM_KEYS:
+        assert np.array_equal(w[k], before[k]), k
+    assert not np.array_equal(port.w1.detach().numpy(), before['linear1.weight'])
+
+
 @pytest.mark.gpu
 def test_chunked_scan_bptt_matches_serial(monkeypatch, golden_weights, golden_erb):
     """The chunked-scan BPTT (aec_train.hip T2a-c, used when T > 64) against
