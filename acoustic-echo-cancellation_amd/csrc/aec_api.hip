@@ -84,8 +84,8 @@ struct aec_handle {
     float* d_dbg = nullptr;      // [2][B][T][32]  (h, mask)
     float2* d_spec = nullptr;    // [B][T][256] NLMS error spectrum (nlms_taps > 0 only)
     // the linear stage's adaptive filter (aec_set_canceller): 0 FD-NLMS, 1 frequency-domain Kalman
-    int kalman = 0;
-    float kal_a = 1.f, kal_p0 = 0.f;
+    CancellerChoice canc;
+    Canceller canceller() const { return make_canceller(cfg, canc); }
     std::vector<int64_t> last_lens;                 // [B][3] of the last call (work lists rebuilt on change)
     int debug = 0;
     int gru_mode = 0;            // AEC_GRU_MODE (A/B builds: timing experiments; results invalid unless 0)
@@ -241,20 +241,14 @@ aec_status aec_set_weights(aec_handle* h, const float* w, size_t n) {
 
 aec_status aec_set_canceller(aec_handle* h, int32_t kind, float a, float p0) {
     if (!h) return AEC_ERR_INVALID_ARG;
-    if (h->cfg.nlms_taps == 0)
-        return fail(h, AEC_ERR_UNSUPPORTED, "no linear stage to select a canceller for (nlms_taps = 0)");
-    if (kind != 0 && kind != 1) return fail(h, AEC_ERR_INVALID_ARG, "canceller kind must be 0 (NLMS) or 1 (Kalman)");
-    if (h->d_state)
-        return fail(h, AEC_ERR_INVALID_ARG, "a streaming state is open: its layout depends on the canceller");
-    if (kind == 1) {
-        if (!(a > 0.f && a <= 1.f))
-            return fail(h, AEC_ERR_INVALID_ARG, "Kalman transition factor a must be in (0, 1]");
-        if (!(p0 >= 0.f && std::isfinite(p0)))
-            return fail(h, AEC_ERR_INVALID_ARG, "Kalman initial covariance p0 must be finite and >= 0");
-        h->kal_a = a;
-        h->kal_p0 = p0;
+    bool unsupported = false;
+    const std::string why = check_canceller(h->cfg.nlms_taps, kind, a, p0, h->d_state != nullptr, &unsupported);
+    if (!why.empty()) return fail(h, unsupported ? AEC_ERR_UNSUPPORTED : AEC_ERR_INVALID_ARG, why);
+    if (kind == kCancellerKalman) {
+        h->canc.a = a;
+        h->canc.p0 = p0;
     }
-    h->kalman = kind;
+    h->canc.kind = kind;
     return AEC_OK;
 }
 
@@ -511,7 +505,7 @@ static aec_status process_impl(aec_handle* h, uint64_t token, const float* mic, 
     AEC_ON_DEVICE(h);
     // which kernels run (aec_host.h); AEC_GRU_NS is a mode knob read per call
     const Plan p = plan_call({h->cfg.nlms_taps, B, h->small_b, h->nlms_mode, h->small_pipe, h->fused, h->gru_mode,
-                              h->num_cus, AEC_MODE_KNOB("AEC_GRU_NS", 0), token != 0, h->kalman});
+                              h->num_cus, AEC_MODE_KNOB("AEC_GRU_NS", 0), token != 0, h->canc.kind});
     if (p.nlms_batch && nlms_smem_bytes(h->sched_len, h->cfg.nlms_taps) > 160 * 1024)   // before any launch
         return fail(h, AEC_ERR_UNSUPPORTED, "erb schedule too long for the NLMS kernel's LDS budget");
     // aec_process_prepared: the look-ahead pass named by `token` (aec_prepare_siglens), checked
@@ -586,8 +580,7 @@ static aec_status process_impl(aec_handle* h, uint64_t token, const float* mic, 
         a.tables = reinterpret_cast<const float*>(h->d_tab);
         a.sched = h->d_sched; a.sched_len = h->sched_len; a.nsig = nsig;
         a.feats = h->d_feats; a.Tmax = Tmax; a.spec = h->d_spec;
-        a.taps = h->cfg.nlms_taps; a.mu = h->cfg.nlms_mu; a.beta = h->cfg.nlms_beta; a.delta = h->cfg.nlms_delta;
-        if (h->kalman) { a.kalman = 1; a.mu = h->kal_a; a.p0 = h->kal_p0; }
+        a.c = h->canceller();
         a.mode = h->nlms_mode;
         a.prio = h->nlms_prio;
         a.erb_role = h->nlms_erb;
@@ -602,19 +595,8 @@ static aec_status process_impl(aec_handle* h, uint64_t token, const float* mic, 
         mark(h, st);
         HIP_TRY(h, launch_analysis(a, st));
         if (p.split && !p.pipe) {      // few streams: recursion per stream, then mic_erb frame-parallel
-            if (h->cfg.nlms_taps > kK2nMaxTaps)      // 9..16 taps: two lanes per bin (aec_longtail.hip)
-                HIP_TRY(h, launch_longtail_recursion(h->d_rows, h->d_spec, h->d_len, Tmax, h->cfg.nlms_taps, h->kalman,
-                                                     h->kalman ? h->kal_a : h->cfg.nlms_mu, h->cfg.nlms_beta,
-                                                     h->cfg.nlms_delta, h->kal_p0, 0, B,
-                                                     h->d_rows + (size_t)B * Tmax * 512, st));
-            else if (h->kalman)
-                HIP_TRY(h, launch_kalman_recursion(h->d_rows, h->d_spec, h->d_len, Tmax, h->cfg.nlms_taps, h->kal_a,
-                                                   h->cfg.nlms_beta, h->cfg.nlms_delta, h->kal_p0, 0, B,
-                                                   h->d_rows + (size_t)B * Tmax * 512, st));
-            else
-                HIP_TRY(h, launch_nlms_recursion(h->d_rows, h->d_spec, h->d_len, Tmax, h->cfg.nlms_taps, h->cfg.nlms_mu,
-                                                 h->cfg.nlms_beta, h->cfg.nlms_delta, 0, B,
-                                                 h->d_rows + (size_t)B * Tmax * 512, st));
+            HIP_TRY(h, launch_recursion({h->d_rows, h->d_spec, h->d_len, Tmax, 0, B, h->d_rows + (size_t)B * Tmax * 512},
+                                        h->canceller(), st));
             HIP_TRY(h, launch_mic_erb(h->d_spec, h->d_feats, h->d_len, Tmax, h->d_sched, h->sched_len, h->d_items,
                                       a.nitems, st));
         }
@@ -637,7 +619,7 @@ static aec_status process_impl(aec_handle* h, uint64_t token, const float* mic, 
         PipeArgs q{};
         q.rows = h->d_rows; q.spec = h->d_spec; q.feats = h->d_feats;
         q.sched = h->d_sched; q.sched_len = h->sched_len;
-        q.mu = h->cfg.nlms_mu; q.beta = h->cfg.nlms_beta; q.delta = h->cfg.nlms_delta;
+        q.c = h->canceller();
         q.progress = h->d_progress; q.epoch = ++h->pipe_epoch; q.err = h->d_pipe_err;
         q.spin_limit = 1 << 20;       // ~1-2 s of polls: far beyond any producer's lead
         // test hook: producers publish nothing and consumers give up after N polls (the timeout path:
@@ -786,11 +768,11 @@ aec_status aec_stream_open(aec_handle* h, int32_t B) {
     HIP_TRY(h, hipDeviceSynchronize());   // a previous state may still be in use
     if (h->d_state) { HIP_TRY(h, hipFree(h->d_state)); h->d_state = nullptr; }
     h->stream_B = 0;
-    const int64_t stride = stream_state_floats(h->cfg.nlms_taps, h->kalman);
+    const int64_t stride = stream_state_floats(h->cfg.nlms_taps, h->canc.kind);
     HIP_TRY(h, hipMalloc(&h->d_state, (size_t)B * stride * sizeof(float)));
     HIP_TRY(h, hipMemset(h->d_state, 0, (size_t)B * stride * sizeof(float)));
-    if (h->kalman) {
-        HIP_TRY(h, launch_stream_cov_fill(h->d_state, stride, 0, B, h->cfg.nlms_taps, h->kal_p0, nullptr));
+    if (h->canc.kind == kCancellerKalman) {
+        HIP_TRY(h, launch_stream_cov_fill(h->d_state, stride, 0, B, h->cfg.nlms_taps, h->canc.p0, nullptr));
         HIP_TRY(h, hipStreamSynchronize(nullptr));
     }
     h->stream_B = B;
@@ -806,9 +788,9 @@ aec_status aec_stream_reset(aec_handle* h, int32_t b, void* stream) {
     const int64_t first = b < 0 ? 0 : b, count = b < 0 ? h->stream_B : 1;
     HIP_TRY(h, hipMemsetAsync(h->d_state + first * h->stream_stride, 0, (size_t)count * h->stream_stride * sizeof(float),
                               reinterpret_cast<hipStream_t>(stream)));
-    if (h->kalman)
+    if (h->canc.kind == kCancellerKalman)
         HIP_TRY(h, launch_stream_cov_fill(h->d_state, h->stream_stride, (int)first, (int)count, h->cfg.nlms_taps,
-                                          h->kal_p0, reinterpret_cast<hipStream_t>(stream)));
+                                          h->canc.p0, reinterpret_cast<hipStream_t>(stream)));
     return AEC_OK;
 }
 
@@ -825,9 +807,8 @@ aec_status aec_stream_step(aec_handle* h, const float* mic, const float* ref, in
     a.state = h->d_state; a.state_stride = h->stream_stride;
     a.w = h->d_w; a.tables = reinterpret_cast<const float*>(h->d_tab);
     a.sched = h->d_sched; a.sched_len = h->sched_len; a.bintab = h->d_bintab;
-    a.mu = h->cfg.nlms_mu; a.beta = h->cfg.nlms_beta; a.delta = h->cfg.nlms_delta;
-    if (h->kalman) { a.kalman = 1; a.mu = h->kal_a; a.p0 = h->kal_p0; }
-    HIP_TRY(h, launch_stream_step(a, h->stream_B, h->cfg.nlms_taps, reinterpret_cast<hipStream_t>(stream)));
+    a.c = h->canceller();
+    HIP_TRY(h, launch_stream_step(a, h->stream_B, reinterpret_cast<hipStream_t>(stream)));
     return AEC_OK;
 }
 
@@ -845,15 +826,14 @@ aec_status aec_stream_push(aec_handle* h, const float* mic, const float* ref, in
     a.s.state = h->d_state; a.s.state_stride = h->stream_stride;
     a.s.w = h->d_w; a.s.tables = reinterpret_cast<const float*>(h->d_tab);
     a.s.sched = h->d_sched; a.s.sched_len = h->sched_len; a.s.bintab = h->d_bintab;
-    a.s.mu = h->cfg.nlms_mu; a.s.beta = h->cfg.nlms_beta; a.s.delta = h->cfg.nlms_delta;
-    if (h->kalman) { a.s.kalman = 1; a.s.mu = h->kal_a; a.s.p0 = h->kal_p0; }
+    a.s.c = h->canceller();
     a.hops = hops; a.max_hops = max_hops;
     // one hop for every stream is the step: the same result from the kernel without the hop loop
     if (!hops && max_hops == 1) {
-        HIP_TRY(h, launch_stream_step(a.s, h->stream_B, h->cfg.nlms_taps, reinterpret_cast<hipStream_t>(stream)));
+        HIP_TRY(h, launch_stream_step(a.s, h->stream_B, reinterpret_cast<hipStream_t>(stream)));
         return AEC_OK;
     }
-    HIP_TRY(h, launch_stream_push(a, h->stream_B, h->cfg.nlms_taps, reinterpret_cast<hipStream_t>(stream)));
+    HIP_TRY(h, launch_stream_push(a, h->stream_B, reinterpret_cast<hipStream_t>(stream)));
     return AEC_OK;
 }
 

@@ -1,0 +1,120 @@
+// aec_canceller.h — the linear stage's canceller as every module sees it: its parameters, the
+// rows of a stream's saved state, and which kernel instantiation a (kind, taps) pair runs.  One
+// owner per decision: the handles store a CancellerChoice, the kernel argument blocks embed a
+// Canceller, the kernels and the host allocations index the state through canceller_rows, and the
+// launchers pick their instantiation through dispatch_canceller.  Plain C++17 with no HIP in it
+// (constexpr functions are usable in device code as they stand), so a host compiler builds it
+// alone and tests/host/canceller_host_check.cpp runs it under the CPU sanitizers.  The per-bin
+// arithmetic is aec_frame.h's (NlmsBin, KalmanBin) and aec_longtail.h's (KalmanHalf).
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <cmath>
+#include <string>
+#include <type_traits>
+
+namespace aec {
+
+// --------------------------------------------------------------------------
+// parameters
+// --------------------------------------------------------------------------
+constexpr int kCancellerNlms = 0;      // FD-NLMS (NlmsBin)
+constexpr int kCancellerKalman = 1;    // frequency-domain Kalman (KalmanBin / KalmanHalf)
+
+// What a kernel needs to run the canceller (passed by value inside the argument blocks).
+struct Canceller {
+    int32_t kind;          // kCancellerNlms / kCancellerKalman
+    int32_t taps;          // 0: no linear stage (the bypass)
+    float gain;            // the NLMS step size mu, or the Kalman transition factor a
+    float beta, delta;     // power / error-power smoothing and regulariser (both kinds)
+    float p0;              // Kalman: initial tap covariance (NlmsBin::reset ignores it)
+};
+static_assert(std::is_trivially_copyable<Canceller>::value, "Canceller travels in kernel argument blocks");
+
+// What aec_set_canceller / aec_crn_set_canceller select; a handle starts with the NLMS.
+struct CancellerChoice {
+    int32_t kind = kCancellerNlms;
+    float a = 1.f, p0 = 0.f;       // the last accepted Kalman values (kept across a switch back to the NLMS)
+};
+
+// CFG: aec_config or aec_crn_config (their nlms_* fields)
+template <class CFG>
+inline Canceller make_canceller(const CFG& cfg, const CancellerChoice& s) {
+    return Canceller{s.kind, cfg.nlms_taps, s.kind == kCancellerKalman ? s.a : cfg.nlms_mu, cfg.nlms_beta,
+                     cfg.nlms_delta, s.p0};
+}
+
+// The setters' argument rules: "" or why the call is refused; *unsupported set when the refusal
+// is AEC_ERR_UNSUPPORTED, not _INVALID_ARG
+inline std::string check_canceller(int taps, int kind, float a, float p0, bool stream_open, bool* unsupported) {
+    *unsupported = false;
+    if (taps == 0) {
+        *unsupported = true;
+        return "no linear stage to select a canceller for (nlms_taps = 0)";
+    }
+    if (kind != 0 && kind != 1) return "canceller kind must be 0 (NLMS) or 1 (Kalman)";
+    if (stream_open) return "a streaming state is open: its layout depends on the canceller";
+    if (kind == 1) {
+        if (!(a > 0.f && a <= 1.f)) return "Kalman transition factor a must be in (0, 1]";
+        if (!(p0 >= 0.f && std::isfinite(p0))) return "Kalman initial covariance p0 must be finite and >= 0";
+    }
+    return "";
+}
+
+// --------------------------------------------------------------------------
+// state layout
+// --------------------------------------------------------------------------
+// One stream's canceller state between streaming calls: rows of kCancellerRow float2 (bin slot k;
+// slot 0 the real pair of bins 0 and 256): W[0 .. taps), the raw far-end history
+// R[t-1 .. t-taps+1], the NLMS power row (unused by the Kalman canceller), then for the Kalman
+// canceller the taps covariance rows P[0 .. taps) and one row psi.  -1: the kind has no such row.
+constexpr int kCancellerRow = 256;
+struct CancellerRows {
+    int w = 0;          // first of `taps` rows
+    int hist = 0;       // first of `nhist` = taps - 1 rows
+    int nhist = 0;
+    int power = 0;
+    int cov = -1;       // Kalman: first of `taps` rows
+    int psi = -1;       // Kalman
+    int rows = 0;       // rows per stream
+    constexpr int64_t floats() const { return (int64_t)rows * kCancellerRow * 2; }
+    constexpr size_t bytes() const { return (size_t)rows * kCancellerRow * 2 * sizeof(float); }
+};
+constexpr CancellerRows canceller_rows(int taps, bool kalman) {
+    CancellerRows r;
+    if (taps <= 0) return r;
+    r.hist = taps;
+    r.nhist = taps - 1;
+    r.power = r.hist + r.nhist;
+    r.rows = r.power + 1;
+    if (kalman) {
+        r.cov = r.rows;
+        r.psi = r.cov + taps;
+        r.rows = r.psi + 1;
+    }
+    return r;
+}
+
+// --------------------------------------------------------------------------
+// dispatch
+// --------------------------------------------------------------------------
+// dispatch_taps calls f(std::integral_constant<int, T>) for T == taps among [LO, HI] and returns
+// its result; `invalid` for any other tap count.  dispatch_canceller adds the kind:
+// f(std::integral_constant<int, T>, std::bool_constant<KALMAN>) for the instantiation that
+// (c.kind, c.taps) names.  A nonzero kind is the Kalman canceller, which has no 0-tap form: a
+// range that starts at 0 (the streaming bypass) does so for the NLMS alone.
+template <int LO, int HI, class R, class F>
+inline R dispatch_taps(int taps, R invalid, F&& f) {
+    static_assert(0 <= LO && LO <= HI, "tap range");
+    if (taps == LO) return f(std::integral_constant<int, LO>{});
+    if constexpr (LO < HI) return dispatch_taps<LO + 1, HI>(taps, invalid, f);
+    return invalid;
+}
+template <int LO, int HI, class R, class F>
+inline R dispatch_canceller(const Canceller& c, R invalid, F&& f) {
+    if (c.kind) return dispatch_taps<(LO > 1 ? LO : 1), HI>(c.taps, invalid, [&](auto t) { return f(t, std::true_type{}); });
+    return dispatch_taps<LO, HI>(c.taps, invalid, [&](auto t) { return f(t, std::false_type{}); });
+}
+
+}  // namespace aec

@@ -7,6 +7,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
+#include "aec_canceller.h"
 #include "aec_fft.h"
 
 namespace aec {
@@ -119,6 +122,8 @@ template <int TAPS>
 struct NlmsBin {
     // K2n's A/B option of running the mic_erb pass on the recursion's waves (erb_role 2) exists for this bin
     static constexpr bool kErbOnNlmsWaves = true;
+    static constexpr int kTaps = TAPS;
+    static constexpr bool kKalman = false;
     float2 w[TAPS];
     float p1[TAPS], p2[TAPS], p4[TAPS];   // operands of R[t], R[t-1], ...
     float qx[TAPS], qy[TAPS];             // per-half |R|^2 of the same entries
@@ -207,9 +212,22 @@ struct NlmsBin {
 // (P p1) p1 + (P p2) p2, which change with P every frame, so the unrolled
 // frame loops have nothing to carry from the frame R entered to the frame it
 // leaves.  One v_rcp_f32 per half and frame; no other division.
+// The Kalman bins' (KalmanBin, aec_longtail.h KalmanHalf) operands of a far-end value r entering
+// the history, and P |R|^2 per half from them
+__device__ __forceinline__ void kalman_hist(bool dual, float2 r, float& p1, float& p2, float& p4) {
+    p1 = r.x;
+    p2 = dual ? 0.f : -r.y;
+    p4 = dual ? r.y : r.x;
+}
+__device__ __forceinline__ float2 kalman_pq(float2 pp, float p1, float p2, float p4) {
+    return make_float2(fmaf(pp.x * p1, p1, (pp.x * p2) * p2), fmaf(pp.y * p4, p4, (pp.y * p2) * p2));
+}
+
 template <int TAPS>
 struct KalmanBin {
     static constexpr bool kErbOnNlmsWaves = false;   // erb_role 2 runs as 1: its loop invariants cost <8> its fit
+    static constexpr int kTaps = TAPS;
+    static constexpr bool kKalman = true;
     float2 w[TAPS];
     float p1[TAPS], p2[TAPS], p4[TAPS];   // operands of R[t], R[t-1], ... (NlmsBin's)
     float2 pp[TAPS];                      // tap covariance P[l] per half
@@ -225,16 +243,8 @@ struct KalmanBin {
         }
         p = make_float2(0.f, 0.f);
     }
-    __device__ __forceinline__ void hist(int l, float2 r) {
-        p1[l] = r.x;
-        p2[l] = dual ? 0.f : -r.y;
-        p4[l] = dual ? r.y : r.x;
-    }
-    // P[l] |R_l|^2 per half
-    __device__ __forceinline__ float2 pq(int l) const {
-        return make_float2(fmaf(pp[l].x * p1[l], p1[l], (pp[l].x * p2[l]) * p2[l]),
-                           fmaf(pp[l].y * p4[l], p4[l], (pp[l].y * p2[l]) * p2[l]));
-    }
+    __device__ __forceinline__ void hist(int l, float2 r) { kalman_hist(dual, r, p1[l], p2[l], p4[l]); }
+    __device__ __forceinline__ float2 pq(int l) const { return kalman_pq(pp[l], p1[l], p2[l], p4[l]); }
     // One frame: returns E = D - sum_l W[l] R[t-l] and adapts W, P, psi.
     __device__ __forceinline__ float2 step(float2 d, float2 r, float a, float beta, float delta) {
 #pragma unroll
@@ -284,6 +294,48 @@ struct KalmanBin {
         return make_float2(ex, ey);
     }
 };
+
+// The bin type dispatch_canceller's constants name (0 taps: a placeholder the bypass never steps)
+template <int TAPS, bool KALMAN>
+using CancellerBin = std::conditional_t<KALMAN, KalmanBin<(TAPS > 0 ? TAPS : 1)>, NlmsBin<(TAPS > 0 ? TAPS : 1)>>;
+
+// Bin slot k of a stream's saved canceller state (nst: the stream's rows, canceller_rows' layout)
+// into a fresh bin and back, for the kernels that restore and save the whole bin in one go.  The
+// history operands are re-derived with step()'s own expressions, and the raw history rows are
+// rebuilt from them (r = (p1, dual ? p4 : -p2): hist() inverted, exact), so any number of
+// steps may lie between the two.
+template <class BIN>
+__device__ __forceinline__ void bin_load(BIN& nb, const float2* nst, int k, float p0) {
+    constexpr CancellerRows R = canceller_rows(BIN::kTaps, BIN::kKalman);
+    nb.reset(k == 0, p0);
+#pragma unroll
+    for (int l = 0; l < BIN::kTaps; ++l) nb.w[l] = nst[(R.w + l) * kCancellerRow + k];
+#pragma unroll
+    for (int l = 0; l < R.nhist; ++l) nb.hist(l, nst[(R.hist + l) * kCancellerRow + k]);
+    if constexpr (BIN::kKalman) {
+#pragma unroll
+        for (int l = 0; l < BIN::kTaps; ++l) nb.pp[l] = nst[(R.cov + l) * kCancellerRow + k];
+        nb.p = nst[R.psi * kCancellerRow + k];
+    } else {
+        nb.p = nst[R.power * kCancellerRow + k];
+    }
+}
+template <class BIN>
+__device__ __forceinline__ void bin_store(const BIN& nb, float2* nst, int k) {
+    constexpr CancellerRows R = canceller_rows(BIN::kTaps, BIN::kKalman);
+#pragma unroll
+    for (int l = 0; l < BIN::kTaps; ++l) nst[(R.w + l) * kCancellerRow + k] = nb.w[l];
+#pragma unroll
+    for (int l = 0; l < R.nhist; ++l)
+        nst[(R.hist + l) * kCancellerRow + k] = make_float2(nb.p1[l], nb.dual ? nb.p4[l] : -nb.p2[l]);
+    if constexpr (BIN::kKalman) {
+#pragma unroll
+        for (int l = 0; l < BIN::kTaps; ++l) nst[(R.cov + l) * kCancellerRow + k] = nb.pp[l];
+        nst[R.psi * kCancellerRow + k] = nb.p;
+    } else {
+        nst[R.power * kCancellerRow + k] = nb.p;
+    }
+}
 
 __device__ __forceinline__ void mags_to_scr(float* scr, int lb, int sw, const float2 (&xa)[8], const float2 (&xb)[8],
                                             float2 x128) {

@@ -200,7 +200,7 @@ __device__ __forceinline__ void pipe_producer(const GruArgs& p, const PipeArgs& 
                 for (int hh = 0; hh < 2; ++hh)
 #pragma unroll
                     for (int i = 0; i < 8; ++i) {
-                        const float2 e = st.step(dd[i], rr[i], q.mu, q.beta, q.delta);
+                        const float2 e = st.step(dd[i], rr[i], q.c.gain, q.c.beta, q.c.delta);
                         er[(8 * hh + i) * 256] = e;
                         fetch((int64_t)c * kCH + 8 * hh + i + 8, i);
                     }

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/aec_hip.h"
+#include "aec_canceller.h"
 
 namespace aec {
 
@@ -23,11 +24,13 @@ constexpr int kK2nMaxTaps = 8;      // most taps K2n (and the per-lane recursion
 constexpr int kMaxTaps = 16;        // most taps of the linear stage (256 ms of far-end history)
 
 inline int64_t num_frames(int64_t n) { return n / 256 + 1; }
-// Floats of one stream's state (aec_stream_*; layout in aec_launch.h): 1024, then one row of 256
-// float2 per canceller field: 2 taps for the NLMS, taps + 1 more (covariances, error power) for
-// the Kalman canceller
+// Floats of one stream's state (aec_stream_*; layout in aec_launch.h): kStreamStatePrefix, then
+// the canceller's rows (aec_canceller.h canceller_rows).  (0 taps with the Kalman kind, which
+// aec_set_canceller refuses, keeps the one row this function has always counted for it.)
+constexpr int kStreamStatePrefix = 1024;
 inline int64_t stream_state_floats(int taps, int kalman = 0) {
-    return 1024 + (int64_t)1024 * taps + (kalman ? (int64_t)512 * (taps + 1) : 0);
+    if (taps <= 0) return kStreamStatePrefix + (kalman ? 2 * kCancellerRow : 0);
+    return kStreamStatePrefix + canceller_rows(taps, kalman != 0).floats();
 }
 inline int64_t out_len(int64_t n) { return 256 * (n / 256); }
 

@@ -35,6 +35,7 @@
 #include "aec_fft.h"
 #include "aec_frame.h"
 #include "aec_launch.h"
+#include "aec_recursion.h"
 #include "aec_stft.h"
 #include "aec_tables.h"
 
@@ -348,7 +349,6 @@ __device__ unsigned long long g_tick[2][kNlmsWavesProf][48][4];
 #else
 #define TICK_STAMP(slot) do {} while (0)
 #endif
-constexpr int kSpecRow = 256;          // float2 per spectrum row
 constexpr int kNlmsWaves = 12;
 constexpr int kERow = 512 + 48;        // floats per LDS error row (split path): 256 float2, then ERB partials
 #ifndef AEC_NLMS_MAGROW
@@ -375,8 +375,7 @@ __device__ __forceinline__ void nlms_transform(float* wr, float* scr, float4 (&p
     rfft_unpack(v, lb, sTw512, xa, xb, x128);
 }
 
-// BIN: the canceller's bin type, NlmsBin<TAPS> or KalmanBin<TAPS> (aec_frame.h; for the latter p.mu
-// carries the transition factor a): the instantiations differ in the recursion's arithmetic and
+// BIN: the canceller's bin type, NlmsBin<TAPS> or KalmanBin<TAPS> (aec_frame.h): the instantiations differ in the recursion's arithmetic and
 // registers only.
 template <class BIN>
 __global__ __launch_bounds__(kNlmsWaves * 64, 1) void nlms_analysis_kernel(NlmsArgs p) {
@@ -436,7 +435,7 @@ __global__ __launch_bounds__(kNlmsWaves * 64, 1) void nlms_analysis_kernel(NlmsA
     const bool al_near = have_near && al_ld && ((reinterpret_cast<uintptr_t>(p.sig[2]) & 15) == 0);
     float2* spec = p.spec + (int64_t)b * p.Tmax * kSpecRow;
     float* feats = p.feats + (int64_t)b * p.Tmax * 96;
-    const float mu = p.mu, beta = p.beta, delta = p.delta;
+    const float mu = p.c.gain, beta = p.c.beta, delta = p.c.delta;
     // mic_erb of chunk c2 from its error rows (complete since the barriers of
     // tick c2 + 1); this group's frame 4 q + gg.  Run by the ref waves
     // (erb_role 1, merged with the ref ERB), by the nlms waves after their
@@ -477,7 +476,7 @@ __global__ __launch_bounds__(kNlmsWaves * 64, 1) void nlms_analysis_kernel(NlmsA
     if (role == 2) {
         const int k = lane + 64 * q;                                  // bin k; k = 0 also bin 256
         BIN st;
-        st.reset(k == 0, p.p0);
+        st.reset(k == 0, p.c.p0);
         float2 dd[kFPB], rr[kFPB];
         for (int c = 0; c < nch + 2; ++c) {
             TICK_STAMP(0);
@@ -716,47 +715,11 @@ __global__ __launch_bounds__(256) void synthesis_kernel(SynthArgs p) {
 // Small-batch NLMS path.  K2n runs one block per stream; with few streams the
 // chip idles and a 10 s stream takes ~0.26 ms (40 ticks).  Here the
 // transforms run frame-parallel in K2 (which also writes the packed mic / ref
-// rows), the recursion is one block per stream over all frames (bin per
-// lane, rows prefetched kRecP frames ahead), and mic_erb = ERB(|E|) runs
+// rows), the recursion is one block per stream over all frames
+// (nlms_recursion_kernel, aec_recursion.h), and mic_erb = ERB(|E|) runs
 // frame-parallel again.  The per-frame arithmetic is K2n's own (NlmsBin,
 // the same row layout and ERB pass), so the output is bit-identical.
 // --------------------------------------------------------------------------
-constexpr int kRecP = 8;
-
-template <class BIN>
-__global__ __launch_bounds__(256) void nlms_recursion_kernel(const float2* __restrict__ rows, float2* __restrict__ spec,
-                                                             const int64_t* __restrict__ lens, int64_t Tmax, float mu,
-                                                             float beta, float delta, int b0, float2* dummy_rows,
-                                                             float p0) {
-    const int b = b0 + blockIdx.x;
-    const int64_t T = lens[b] / kHop + 1;
-    const int k = threadIdx.x;
-    const float2* r0 = rows + (int64_t)b * Tmax * 512;
-    float2* e0 = spec + (int64_t)b * Tmax * kSpecRow;
-    BIN st;
-    st.reset(k == 0, p0);
-    float2 dd[kRecP], rr[kRecP];
-    auto fetch = [&](int64_t t, int i) {                  // rows past the end: any valid row (results unused)
-        const int64_t tc = t < T ? t : T - 1;
-        dd[i] = r0[tc * 512 + k];
-        rr[i] = r0[tc * 512 + 256 + k];
-    };
-    // frames past the end store to this stream's dummy row (after the [B][Tmax][2][256]
-    // rows): every store is unconditional, so the compiler's vmcnt bookkeeping
-    // stays exact across the loop and the prefetched rows are not waited for early
-    float2* dummy = dummy_rows + (int64_t)b * 256 + k;
-#pragma unroll
-    for (int i = 0; i < kRecP; ++i) fetch(i, i);
-    for (int64_t t0 = 0; t0 < T; t0 += kRecP) {
-#pragma unroll
-        for (int i = 0; i < kRecP; ++i) {
-            const float2 e = st.step(dd[i], rr[i], mu, beta, delta);
-            *(t0 + i < T ? e0 + (t0 + i) * kSpecRow + k : dummy) = e;
-            fetch(t0 + i + kRecP, i);
-        }
-    }
-}
-
 // mic_erb of every frame from its E row (K2n's mic_erb pass, frame-parallel):
 // one 4-frame work item per wave, 4 waves per block
 __global__ __launch_bounds__(256) void mic_erb_kernel(const float2* __restrict__ spec, float* __restrict__ feats,
@@ -785,35 +748,12 @@ __global__ __launch_bounds__(256) void mic_erb_kernel(const float2* __restrict__
     erb_project(er, sSched, sComb, L, lb, sw, t < T ? feats + ((int64_t)it.b * Tmax + t) * 96 : nullptr);
 }
 
-hipError_t launch_nlms_recursion(const float2* rows, float2* spec, const int64_t* lens, int64_t Tmax, int taps,
-                                 float mu, float beta, float delta, int b0, int nb, float2* dummy_rows, hipStream_t st) {
-    if (nb <= 0) return hipSuccess;
-    switch (taps) {
-#define AEC_REC_CASE(T)                                                                                          \
-        case T: hipLaunchKernelGGL(nlms_recursion_kernel<NlmsBin<T>>, dim3(nb), dim3(256), 0, st, rows, spec, lens, \
-                                   Tmax, mu, beta, delta, b0, dummy_rows, 0.f); break;
-        AEC_REC_CASE(1) AEC_REC_CASE(2) AEC_REC_CASE(3) AEC_REC_CASE(4)
-        AEC_REC_CASE(5) AEC_REC_CASE(6) AEC_REC_CASE(7) AEC_REC_CASE(8)
-#undef AEC_REC_CASE
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_kalman_recursion(const float2* rows, float2* spec, const int64_t* lens, int64_t Tmax, int taps,
-                                   float a, float beta, float delta, float p0, int b0, int nb, float2* dummy_rows,
-                                   hipStream_t st) {
-    if (nb <= 0) return hipSuccess;
-    switch (taps) {
-#define AEC_REC_CASE(T)                                                                                            \
-        case T: hipLaunchKernelGGL(nlms_recursion_kernel<KalmanBin<T>>, dim3(nb), dim3(256), 0, st, rows, spec, lens, \
-                                   Tmax, a, beta, delta, b0, dummy_rows, p0); break;
-        AEC_REC_CASE(1) AEC_REC_CASE(2) AEC_REC_CASE(3) AEC_REC_CASE(4)
-        AEC_REC_CASE(5) AEC_REC_CASE(6) AEC_REC_CASE(7) AEC_REC_CASE(8)
-#undef AEC_REC_CASE
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+hipError_t launch_recursion(const RecursionArgs& a, const Canceller& c, hipStream_t st) {
+    if (a.nb <= 0) return hipSuccess;
+    if (c.taps > kK2nMaxTaps) return launch_recursion_long(a, c, st);      // aec_longtail.hip
+    return dispatch_canceller<1, kK2nMaxTaps>(c, hipErrorInvalidValue, [&](auto taps, auto kalman) {
+        return launch_recursion_lanes<CancellerBin<decltype(taps)::value, decltype(kalman)::value>>(a, c, st);
+    });
 }
 
 hipError_t launch_mic_erb(const float2* spec, float* feats, const int64_t* lens, int64_t Tmax, const float* sched,
@@ -883,37 +823,16 @@ static hipError_t launch_nlms_t(const NlmsArgs& a, int nb, hipStream_t st) {
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(nlms_analysis_kernel<BIN>),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL(nlms_analysis_kernel<BIN>, dim3(nb), dim3(kNlmsWaves * 64), nlms_smem_bytes(a.sched_len, a.taps),
+    hipLaunchKernelGGL(nlms_analysis_kernel<BIN>, dim3(nb), dim3(kNlmsWaves * 64), nlms_smem_bytes(a.sched_len, a.c.taps),
                        st, a);
     return hipGetLastError();
 }
 
 hipError_t launch_nlms_analysis(const NlmsArgs& a, int nb, hipStream_t st) {
     if (nb <= 0) return hipSuccess;
-    if (a.kalman) {
-        switch (a.taps) {
-            case 1: return launch_nlms_t<KalmanBin<1>>(a, nb, st);
-            case 2: return launch_nlms_t<KalmanBin<2>>(a, nb, st);
-            case 3: return launch_nlms_t<KalmanBin<3>>(a, nb, st);
-            case 4: return launch_nlms_t<KalmanBin<4>>(a, nb, st);
-            case 5: return launch_nlms_t<KalmanBin<5>>(a, nb, st);
-            case 6: return launch_nlms_t<KalmanBin<6>>(a, nb, st);
-            case 7: return launch_nlms_t<KalmanBin<7>>(a, nb, st);
-            case 8: return launch_nlms_t<KalmanBin<8>>(a, nb, st);
-            default: return hipErrorInvalidValue;
-        }
-    }
-    switch (a.taps) {
-        case 1: return launch_nlms_t<NlmsBin<1>>(a, nb, st);
-        case 2: return launch_nlms_t<NlmsBin<2>>(a, nb, st);
-        case 3: return launch_nlms_t<NlmsBin<3>>(a, nb, st);
-        case 4: return launch_nlms_t<NlmsBin<4>>(a, nb, st);
-        case 5: return launch_nlms_t<NlmsBin<5>>(a, nb, st);
-        case 6: return launch_nlms_t<NlmsBin<6>>(a, nb, st);
-        case 7: return launch_nlms_t<NlmsBin<7>>(a, nb, st);
-        case 8: return launch_nlms_t<NlmsBin<8>>(a, nb, st);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_canceller<1, kK2nMaxTaps>(a.c, hipErrorInvalidValue, [&](auto taps, auto kalman) {
+        return launch_nlms_t<CancellerBin<decltype(taps)::value, decltype(kalman)::value>>(a, nb, st);
+    });
 }
 
 }  // namespace aec

@@ -51,15 +51,12 @@ struct NlmsArgs {
     float* feats;            // [B][Tmax][96]
     int64_t Tmax;
     float2* spec;            // [B][Tmax][256] error spectrum E (slot 0 = (E[0], E[256]))
-    int taps;
-    float mu, beta, delta;
+    Canceller c;             // 1..kK2nMaxTaps taps: nlms_analysis_kernel<NlmsBin<taps>> or <KalmanBin<taps>>
     int prio;                // wave priorities (AEC_NLMS_PRIO, decimal digits mic|ref|nlms, 0..3 each)
     int erb_role;            // waves that run the mic_erb pass: 0 mic if no near (else ref), 1 ref, 2 nlms
     int mode;                // timing experiments only (AEC_NLMS_MODE): bit0 skip recursion,
                              // bit1 skip near transform, bit2 skip mic ERB, bit3 skip mic/ref transforms;
                              // bit4 (valid results): the ref waves' two ERB projections in two passes
-    int kalman;              // 1: the Kalman canceller (nlms_analysis_kernel<KalmanBin<taps>>): mu carries its
-    float p0;                //    transition factor a, p0 the initial tap covariance
 };
 
 struct GruArgs {
@@ -102,14 +99,11 @@ struct SynthArgs {
 //   [0, 512)     previous input hop: mic (256), ref (256)
 //   [512, 768)   OLA tail: second half of the previous synthesis frame
 //   [768, 800)   GRU h
-//   [1024, ...)  canceller, rows of float2[256] by field: w[0..taps-1],
-//                far-end history r[t-1 .. t-taps+1], NLMS power p (row 2 taps - 1,
-//                unused by the Kalman canceller); Kalman: tap covariances
-//                P[0..taps-1] (rows 2 taps ..), error power psi (row 3 taps)
+//   [1024, ...)  canceller: canceller_rows(taps, kalman) (aec_canceller.h)
 constexpr int kStPrev = 0;
 constexpr int kStTail = 512;
 constexpr int kStH = 768;
-constexpr int kStNlms = 1024;
+constexpr int kStNlms = kStreamStatePrefix;
 
 struct StreamStepArgs {
     const float* mic;        // [B][ld_in] hop k of every stream
@@ -124,9 +118,7 @@ struct StreamStepArgs {
     const float* sched;
     int sched_len;
     const float* bintab;
-    float mu, beta, delta;
-    int kalman;              // 1: the Kalman canceller: mu carries its transition factor a,
-    float p0;                //    p0 the initial tap covariance
+    Canceller c;             // 0 taps (NLMS kind only): the bypass
 };
 
 // A packet of hops per stream in one launch (aec_stream.hip, aec_stream_push): s.mic / s.ref rows
@@ -166,27 +158,30 @@ hipError_t launch_nlms_analysis(const NlmsArgs& a, int nb, hipStream_t st);
 // small-batch NLMS path (few streams: the per-stream K2n block would leave the
 // chip idle): K2 with spectrum rows, then the recursion per (stream, bin) and
 // the mic_erb pass over all frames
-hipError_t launch_nlms_recursion(const float2* rows, float2* spec, const int64_t* lens, int64_t Tmax, int taps,
-                                 float mu, float beta, float delta, int b0, int nb, float2* dummy_rows, hipStream_t st);
-hipError_t launch_kalman_recursion(const float2* rows, float2* spec, const int64_t* lens, int64_t Tmax, int taps,
-                                   float a, float beta, float delta, float p0, int b0, int nb, float2* dummy_rows,
-                                   hipStream_t st);
-// 9..16 taps (aec_longtail.hip): the recursion of the split path; the Kalman canceller with two
-// lanes per bin, each running one of the two partial chains of KalmanBin::step (mu carries a)
-hipError_t launch_longtail_recursion(const float2* rows, float2* spec, const int64_t* lens, int64_t Tmax, int taps,
-                                     int kalman, float mu, float beta, float delta, float p0, int b0, int nb,
-                                     float2* dummy_rows, hipStream_t st);
+struct RecursionArgs {
+    const float2* rows;      // K2's packed mic / ref rows [B][Tmax][2][256]
+    float2* spec;            // E rows [B][Tmax][256] (out)
+    const int64_t* lens;
+    int64_t Tmax;
+    int b0, nb;              // block i runs stream b0 + i
+    float2* dummy_rows;      // [B][256]: where frames past a stream's end are stored
+};
+// 1..8 taps: one lane per bin (aec_kernels.hip); 9..16 (aec_longtail.hip): the NLMS the same, the
+// Kalman canceller with two lanes per bin, each running one of the two partial chains of
+// KalmanBin::step.  launch_recursion forwards to launch_recursion_long above kK2nMaxTaps.
+hipError_t launch_recursion(const RecursionArgs& a, const Canceller& c, hipStream_t st);
+hipError_t launch_recursion_long(const RecursionArgs& a, const Canceller& c, hipStream_t st);
 hipError_t launch_mic_erb(const float2* spec, float* feats, const int64_t* lens, int64_t Tmax, const float* sched,
                           int sched_len, const WorkItem* items, int64_t nitems, hipStream_t st);
 hipError_t launch_gru(const GruArgs& a, int B, hipStream_t st);
 hipError_t launch_synthesis(const SynthArgs& a, hipStream_t st);
-hipError_t launch_stream_step(const StreamStepArgs& a, int B, int taps, hipStream_t st);
-hipError_t launch_stream_push(const StreamPushArgs& a, int B, int taps, hipStream_t st);
+hipError_t launch_stream_step(const StreamStepArgs& a, int B, hipStream_t st);
+hipError_t launch_stream_push(const StreamPushArgs& a, int B, hipStream_t st);
 hipError_t launch_stream_cov_fill(float* state, int64_t stride, int first, int count, int taps, float p0,
                                   hipStream_t st);
 // 9..16 taps (aec_stream_long.hip): the same kernel templates; launch_stream_step / _push forward here
-hipError_t launch_stream_step_long(const StreamStepArgs& a, int B, int taps, hipStream_t st);
-hipError_t launch_stream_push_long(const StreamPushArgs& a, int B, int taps, hipStream_t st);
+hipError_t launch_stream_step_long(const StreamStepArgs& a, int B, hipStream_t st);
+hipError_t launch_stream_push_long(const StreamPushArgs& a, int B, hipStream_t st);
 // K3+K4 fused (aec_gru_synth.hip): GRU + head + synthesis of the NLMS error spectrum, one stream per
 // block or two (Plan::gru_one, aec_host.h)
 hipError_t launch_gru_synth(const GruArgs& g, const SynthArgs& y, int B, bool one_per_block, hipStream_t st);
@@ -198,7 +193,7 @@ struct PipeArgs {
     float* feats;                     // mic_erb = feats[b][t][0:32] (out)
     const float* sched;               // ERB schedule (aec_tables.h)
     int sched_len;
-    float mu, beta, delta;
+    Canceller c;                      // the NLMS at kPipeTaps (plan_call, aec_host.h)
     unsigned long long* progress;     // [B]: (epoch << 32) | chunks of the stream published
     unsigned long long epoch;         // this launch's epoch (per handle, increasing)
     int* err;                         // host-mapped word: a consumer wave gave up waiting

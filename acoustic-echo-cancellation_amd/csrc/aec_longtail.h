@@ -56,16 +56,8 @@ struct KalmanHalf {
         }
         p = make_float2(0.f, 0.f);
     }
-    __device__ __forceinline__ void hist(int l, float2 r) {
-        p1[l] = r.x;
-        p2[l] = dual ? 0.f : -r.y;
-        p4[l] = dual ? r.y : r.x;
-    }
-    // KalmanBin::pq
-    __device__ __forceinline__ float2 pq(int l) const {
-        return make_float2(fmaf(pp[l].x * p1[l], p1[l], (pp[l].x * p2[l]) * p2[l]),
-                           fmaf(pp[l].y * p4[l], p4[l], (pp[l].y * p2[l]) * p2[l]));
-    }
+    __device__ __forceinline__ void hist(int l, float2 r) { kalman_hist(dual, r, p1[l], p2[l], p4[l]); }
+    __device__ __forceinline__ float2 pq(int l) const { return kalman_pq(pp[l], p1[l], p2[l], p4[l]); }
     __device__ __forceinline__ float2 step(float2 d, float2 r, float a, float beta, float delta) {
 #pragma unroll
         for (int l = H - 1; l >= 1; --l) {

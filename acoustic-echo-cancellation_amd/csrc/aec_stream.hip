@@ -29,12 +29,13 @@
 
 namespace aec {
 
-// A fresh Kalman state is zero except the tap covariances P[l] = p0 (rows 2 taps .. 3 taps - 1 of
-// the canceller block): `count` streams from `first`
+// A fresh Kalman state is zero except the tap covariances P[l] = p0 (the cov rows of the canceller
+// block): `count` streams from `first`
 __global__ __launch_bounds__(256) void stream_cov_fill_kernel(float* state, int64_t stride, int first, int taps,
                                                               float p0) {
     float2* nst = reinterpret_cast<float2*>(state + (int64_t)(first + blockIdx.x) * stride + kStNlms);
-    for (int l = 0; l < taps; ++l) nst[(2 * taps + l) * 256 + threadIdx.x] = make_float2(p0, p0);
+    const int cov = canceller_rows(taps, true).cov;
+    for (int l = 0; l < taps; ++l) nst[(cov + l) * 256 + threadIdx.x] = make_float2(p0, p0);
 }
 
 hipError_t launch_stream_cov_fill(float* state, int64_t stride, int first, int count, int taps, float p0,
@@ -44,56 +45,18 @@ hipError_t launch_stream_cov_fill(float* state, int64_t stride, int first, int c
     return hipGetLastError();
 }
 
-hipError_t launch_stream_step(const StreamStepArgs& a, int B, int taps, hipStream_t s) {
+hipError_t launch_stream_step(const StreamStepArgs& a, int B, hipStream_t s) {
     if (B <= 0) return hipSuccess;
     if (a.sched_len > kSchedMax) return hipErrorInvalidValue;
-    if (taps > 8) return launch_stream_step_long(a, B, taps, s);       // aec_stream_long.hip
-    if (a.kalman) {
-        switch (taps) {
-#define AEC_STREAM_CASE(T) \
-            case T: hipLaunchKernelGGL((stream_step_kernel<T, true>), dim3(B), dim3(kStreamThreads), 0, s, a); break;
-            AEC_STREAM_CASE(1) AEC_STREAM_CASE(2) AEC_STREAM_CASE(3) AEC_STREAM_CASE(4)
-            AEC_STREAM_CASE(5) AEC_STREAM_CASE(6) AEC_STREAM_CASE(7) AEC_STREAM_CASE(8)
-#undef AEC_STREAM_CASE
-            default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    switch (taps) {
-#define AEC_STREAM_CASE(T) \
-        case T: hipLaunchKernelGGL(stream_step_kernel<T>, dim3(B), dim3(kStreamThreads), 0, s, a); break;
-        AEC_STREAM_CASE(0) AEC_STREAM_CASE(1) AEC_STREAM_CASE(2) AEC_STREAM_CASE(3) AEC_STREAM_CASE(4)
-        AEC_STREAM_CASE(5) AEC_STREAM_CASE(6) AEC_STREAM_CASE(7) AEC_STREAM_CASE(8)
-#undef AEC_STREAM_CASE
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    if (a.c.taps > 8) return launch_stream_step_long(a, B, s);       // aec_stream_long.hip
+    return launch_stream_step_range<0, 8>(a, B, s);
 }
 
-hipError_t launch_stream_push(const StreamPushArgs& a, int B, int taps, hipStream_t s) {
+hipError_t launch_stream_push(const StreamPushArgs& a, int B, hipStream_t s) {
     if (B <= 0) return hipSuccess;
     if (a.s.sched_len > kSchedMax || a.max_hops < 1) return hipErrorInvalidValue;
-    if (taps > 8) return launch_stream_push_long(a, B, taps, s);
-    if (a.s.kalman) {
-        switch (taps) {
-#define AEC_STREAM_CASE(T) \
-            case T: hipLaunchKernelGGL((stream_push_kernel<T, true>), dim3(B), dim3(kStreamThreads), 0, s, a); break;
-            AEC_STREAM_CASE(1) AEC_STREAM_CASE(2) AEC_STREAM_CASE(3) AEC_STREAM_CASE(4)
-            AEC_STREAM_CASE(5) AEC_STREAM_CASE(6) AEC_STREAM_CASE(7) AEC_STREAM_CASE(8)
-#undef AEC_STREAM_CASE
-            default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    switch (taps) {
-#define AEC_STREAM_CASE(T) \
-        case T: hipLaunchKernelGGL(stream_push_kernel<T>, dim3(B), dim3(kStreamThreads), 0, s, a); break;
-        AEC_STREAM_CASE(0) AEC_STREAM_CASE(1) AEC_STREAM_CASE(2) AEC_STREAM_CASE(3) AEC_STREAM_CASE(4)
-        AEC_STREAM_CASE(5) AEC_STREAM_CASE(6) AEC_STREAM_CASE(7) AEC_STREAM_CASE(8)
-#undef AEC_STREAM_CASE
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    if (a.s.c.taps > 8) return launch_stream_push_long(a, B, s);
+    return launch_stream_push_range<0, 8>(a, B, s);
 }
 
 }  // namespace aec

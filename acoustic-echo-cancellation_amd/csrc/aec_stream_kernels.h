@@ -5,8 +5,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <type_traits>
-
 #include "aec_fft.h"
 #include "aec_frame.h"
 #include "aec_launch.h"
@@ -18,7 +16,7 @@ namespace aec {
 constexpr int kStreamThreads = 256;
 constexpr int kSchedMax = 48;                 // ErbTables: L <= 48
 
-// KALMAN: the canceller is KalmanBin (p.mu carries its transition factor a), else NlmsBin
+// KALMAN: the canceller is KalmanBin, else NlmsBin (CancellerBin); state rows: canceller_rows
 template <int TAPS, bool KALMAN = false>
 __global__ __launch_bounds__(kStreamThreads) void stream_step_kernel(StreamStepArgs p) {
     __shared__ __attribute__((aligned(16))) float4 sSched[kSchedMax * 16];
@@ -90,33 +88,34 @@ __global__ __launch_bounds__(kStreamThreads) void stream_step_kernel(StreamStepA
 
     // NLMS bin slot k = tid (slot 0: the real pair (0, 256)); taps, power and
     // the raw far-end history r[t-1 .. t-TAPS+1] from the state
-    std::conditional_t<KALMAN, KalmanBin<TAPS ? TAPS : 1>, NlmsBin<TAPS ? TAPS : 1>> nb;
+    constexpr CancellerRows R = canceller_rows(TAPS, KALMAN);
+    CancellerBin<TAPS, KALMAN> nb;
     float2 rh[TAPS > 1 ? TAPS - 1 : 1];
     float2* nst = reinterpret_cast<float2*>(st + kStNlms);
     if constexpr (TAPS > 0) {
-        nb.reset(tid == 0, p.p0);
+        nb.reset(tid == 0, p.c.p0);
 #pragma unroll
         for (int l = 0; l < TAPS; ++l) {
-            const float2 w = nst[l * 256 + tid];
+            const float2 w = nst[(R.w + l) * 256 + tid];
             nb.w[l] = w;
         }
 #pragma unroll
-        for (int l = 0; l + 1 < TAPS; ++l) {
+        for (int l = 0; l < R.nhist; ++l) {
             // the operands step() derived from r when r entered (same expressions)
-            const float2 r2 = nst[(TAPS + l) * 256 + tid];
+            const float2 r2 = nst[(R.hist + l) * 256 + tid];
             rh[l] = r2;
             nb.hist(l, r2);
         }
         if constexpr (KALMAN) {
 #pragma unroll
             for (int l = 0; l < TAPS; ++l) {
-                const float2 c = nst[(2 * TAPS + l) * 256 + tid];
+                const float2 c = nst[(R.cov + l) * 256 + tid];
                 nb.pp[l] = c;
             }
-            const float2 psi = nst[3 * TAPS * 256 + tid];
+            const float2 psi = nst[R.psi * 256 + tid];
             nb.p = psi;
         } else {
-            const float2 pp = nst[(2 * TAPS - 1) * 256 + tid];
+            const float2 pp = nst[R.power * 256 + tid];
             nb.p = pp;
         }
     }
@@ -172,21 +171,21 @@ __global__ __launch_bounds__(kStreamThreads) void stream_step_kernel(StreamStepA
 
     // ---- P2: NLMS step of every bin (E row) ----
     if constexpr (TAPS > 0) {
-        const float2 e = nb.step(sRow[0][tid], sRow[1][tid], p.mu, p.beta, p.delta);
+        const float2 e = nb.step(sRow[0][tid], sRow[1][tid], p.c.gain, p.c.beta, p.c.delta);
         sRow[2][tid] = e;
 #pragma unroll
-        for (int l = 0; l < TAPS; ++l) nst[l * 256 + tid] = nb.w[l];
+        for (int l = 0; l < TAPS; ++l) nst[(R.w + l) * 256 + tid] = nb.w[l];
         if constexpr (TAPS > 1) {
-            nst[TAPS * 256 + tid] = sRow[1][tid];
+            nst[R.hist * 256 + tid] = sRow[1][tid];
 #pragma unroll
-            for (int l = 1; l + 1 < TAPS; ++l) nst[(TAPS + l) * 256 + tid] = rh[l - 1];
+            for (int l = 1; l < R.nhist; ++l) nst[(R.hist + l) * 256 + tid] = rh[l - 1];
         }
         if constexpr (KALMAN) {
 #pragma unroll
-            for (int l = 0; l < TAPS; ++l) nst[(2 * TAPS + l) * 256 + tid] = nb.pp[l];
-            nst[3 * TAPS * 256 + tid] = nb.p;
+            for (int l = 0; l < TAPS; ++l) nst[(R.cov + l) * 256 + tid] = nb.pp[l];
+            nst[R.psi * 256 + tid] = nb.p;
         } else {
-            nst[(2 * TAPS - 1) * 256 + tid] = nb.p;
+            nst[R.power * 256 + tid] = nb.p;
         }
         __syncthreads();
     }
@@ -250,7 +249,7 @@ __global__ __launch_bounds__(kStreamThreads) void stream_step_kernel(StreamStepA
 // last hop, in aec_launch.h's layout.  Between the hops of a packet
 //   - the canceller lives in the bin object, its far-end history rotating in step() as in the batch
 //     kernels; the raw history rows of the state are rebuilt from the operands at the end
-//     (r = (p1, dual ? p4 : -p2): hist()'s expressions inverted, exact),
+//     (bin_store, aec_frame.h),
 //   - the OLA tail and this thread's sample of the current hop stay in registers, the GRU h
 //     alternates between the two rows of sH,
 //   - hop j+1's samples are loaded into registers before hop j's P1 and staged in hop j's P8.
@@ -332,22 +331,9 @@ __global__ __launch_bounds__(kStreamThreads) void stream_push_kernel(StreamPushA
     float tail = st[kStTail + tid];
 
     // canceller bin slot k = tid (slot 0: the real pair (0, 256)), as the step loads it
-    std::conditional_t<KALMAN, KalmanBin<TAPS ? TAPS : 1>, NlmsBin<TAPS ? TAPS : 1>> nb;
+    CancellerBin<TAPS, KALMAN> nb;
     float2* nst = reinterpret_cast<float2*>(st + kStNlms);
-    if constexpr (TAPS > 0) {
-        nb.reset(tid == 0, p.p0);
-#pragma unroll
-        for (int l = 0; l < TAPS; ++l) nb.w[l] = nst[l * 256 + tid];
-#pragma unroll
-        for (int l = 0; l + 1 < TAPS; ++l) nb.hist(l, nst[(TAPS + l) * 256 + tid]);
-        if constexpr (KALMAN) {
-#pragma unroll
-            for (int l = 0; l < TAPS; ++l) nb.pp[l] = nst[(2 * TAPS + l) * 256 + tid];
-            nb.p = nst[3 * TAPS * 256 + tid];
-        } else {
-            nb.p = nst[(2 * TAPS - 1) * 256 + tid];
-        }
-    }
+    if constexpr (TAPS > 0) bin_load(nb, nst, tid, p.c.p0);
 
     // role weights: the step's three sets (wave 0: W_hh k-halves; threads 64..159: a W_ih row; wave 3:
     // the head's rows) in ONE register array, since a thread has one role and the sets stay live
@@ -410,7 +396,7 @@ __global__ __launch_bounds__(kStreamThreads) void stream_push_kernel(StreamPushA
 
         // ---- P2: canceller step of every bin (E row); the state stays in registers ----
         if constexpr (TAPS > 0) {
-            sRow[2][tid] = nb.step(sRow[0][tid], sRow[1][tid], p.mu, p.beta, p.delta);
+            sRow[2][tid] = nb.step(sRow[0][tid], sRow[1][tid], p.c.gain, p.c.beta, p.c.delta);
             __syncthreads();
         }
 
@@ -489,20 +475,23 @@ __global__ __launch_bounds__(kStreamThreads) void stream_push_kernel(StreamPushA
     st[kStPrev + 256 + tid] = cr;
     st[kStTail + tid] = tail;
     if (tid < 32) st[kStH + tid] = sH[n & 1][tid];
-    if constexpr (TAPS > 0) {
-#pragma unroll
-        for (int l = 0; l < TAPS; ++l) nst[l * 256 + tid] = nb.w[l];
-#pragma unroll
-        for (int l = 0; l + 1 < TAPS; ++l)
-            nst[(TAPS + l) * 256 + tid] = make_float2(nb.p1[l], nb.dual ? nb.p4[l] : -nb.p2[l]);
-        if constexpr (KALMAN) {
-#pragma unroll
-            for (int l = 0; l < TAPS; ++l) nst[(2 * TAPS + l) * 256 + tid] = nb.pp[l];
-            nst[3 * TAPS * 256 + tid] = nb.p;
-        } else {
-            nst[(2 * TAPS - 1) * 256 + tid] = nb.p;
-        }
-    }
+    if constexpr (TAPS > 0) bin_store(nb, nst, tid);
+}
+
+// The launches of one translation unit's tap range [LO, HI]
+template <int LO, int HI>
+hipError_t launch_stream_step_range(const StreamStepArgs& a, int B, hipStream_t s) {
+    return dispatch_canceller<LO, HI>(a.c, hipErrorInvalidValue, [&](auto taps, auto kalman) {
+        hipLaunchKernelGGL((stream_step_kernel<decltype(taps)::value, decltype(kalman)::value>), dim3(B), dim3(kStreamThreads), 0, s, a);
+        return hipGetLastError();
+    });
+}
+template <int LO, int HI>
+hipError_t launch_stream_push_range(const StreamPushArgs& a, int B, hipStream_t s) {
+    return dispatch_canceller<LO, HI>(a.s.c, hipErrorInvalidValue, [&](auto taps, auto kalman) {
+        hipLaunchKernelGGL((stream_push_kernel<decltype(taps)::value, decltype(kalman)::value>), dim3(B), dim3(kStreamThreads), 0, s, a);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace aec

@@ -10,54 +10,16 @@
 
 namespace aec {
 
-#define AEC_STREAM_LONG_CASES \
-    AEC_STREAM_CASE(9) AEC_STREAM_CASE(10) AEC_STREAM_CASE(11) AEC_STREAM_CASE(12) \
-    AEC_STREAM_CASE(13) AEC_STREAM_CASE(14) AEC_STREAM_CASE(15) AEC_STREAM_CASE(16)
-
-hipError_t launch_stream_step_long(const StreamStepArgs& a, int B, int taps, hipStream_t s) {
+hipError_t launch_stream_step_long(const StreamStepArgs& a, int B, hipStream_t s) {
     if (B <= 0) return hipSuccess;
     if (a.sched_len > kSchedMax) return hipErrorInvalidValue;
-    if (a.kalman) {
-        switch (taps) {
-#define AEC_STREAM_CASE(T) \
-            case T: hipLaunchKernelGGL((stream_step_kernel<T, true>), dim3(B), dim3(kStreamThreads), 0, s, a); break;
-            AEC_STREAM_LONG_CASES
-#undef AEC_STREAM_CASE
-            default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    switch (taps) {
-#define AEC_STREAM_CASE(T) \
-        case T: hipLaunchKernelGGL(stream_step_kernel<T>, dim3(B), dim3(kStreamThreads), 0, s, a); break;
-        AEC_STREAM_LONG_CASES
-#undef AEC_STREAM_CASE
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return launch_stream_step_range<9, 16>(a, B, s);
 }
 
-hipError_t launch_stream_push_long(const StreamPushArgs& a, int B, int taps, hipStream_t s) {
+hipError_t launch_stream_push_long(const StreamPushArgs& a, int B, hipStream_t s) {
     if (B <= 0) return hipSuccess;
     if (a.s.sched_len > kSchedMax || a.max_hops < 1) return hipErrorInvalidValue;
-    if (a.s.kalman) {
-        switch (taps) {
-#define AEC_STREAM_CASE(T) \
-            case T: hipLaunchKernelGGL((stream_push_kernel<T, true>), dim3(B), dim3(kStreamThreads), 0, s, a); break;
-            AEC_STREAM_LONG_CASES
-#undef AEC_STREAM_CASE
-            default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    switch (taps) {
-#define AEC_STREAM_CASE(T) \
-        case T: hipLaunchKernelGGL(stream_push_kernel<T>, dim3(B), dim3(kStreamThreads), 0, s, a); break;
-        AEC_STREAM_LONG_CASES
-#undef AEC_STREAM_CASE
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return launch_stream_push_range<9, 16>(a, B, s);
 }
 
 }  // namespace aec

@@ -92,8 +92,8 @@ struct aec_crn_handle : Net<Packed> {              // cfg, the derived sizes and
     std::vector<void*> allocs;
     StreamState* ss = nullptr;                     // aec_crn_stream_* state
     // the linear stage's adaptive filter (aec_crn_set_canceller): 0 FD-NLMS, 1 frequency-domain Kalman
-    int kalman = 0;
-    float kal_a = 1.f, kal_p0 = 0.f;
+    aec::CancellerChoice canc;
+    aec::Canceller canceller() const { return aec::make_canceller(cfg, canc); }
     // persistent LSTM recurrence (crn_persist.hip; AEC_CRN_PERSIST=0: one launch per frame)
     int persist = 1;
     int num_cus = 0;
@@ -534,12 +534,7 @@ static aec_status run(aec_crn_handle* h, const float* mic, const float* far, int
     if (c.nlms_taps > 0) fa.rows = h->nrows;
     CRN_TRY(h, crn::launch_front<T>(fa, B, st));
     if (c.nlms_taps > 0) {   // canceller: rows -> E rows (one block per stream) -> X0
-        if (h->kalman)
-            CRN_TRY(h, aec::launch_kalman_recursion(h->nrows, h->espec, h->d_len, Tmax, c.nlms_taps, h->kal_a, c.nlms_beta,
-                                                    c.nlms_delta, h->kal_p0, 0, B, h->ndummy, st));
-        else
-            CRN_TRY(h, aec::launch_nlms_recursion(h->nrows, h->espec, h->d_len, Tmax, c.nlms_taps, c.nlms_mu, c.nlms_beta,
-                                                  c.nlms_delta, 0, B, h->ndummy, st));
+        CRN_TRY(h, aec::launch_recursion({h->nrows, h->espec, h->d_len, Tmax, 0, B, h->ndummy}, h->canceller(), st));
         crn::RowsX0Args xa{h->nrows, h->espec, h->d_len, Tmax, bf.x0, B};
         CRN_TRY(h, crn::launch_rows_x0<T>(xa, st));
     }
@@ -736,7 +731,7 @@ static aec_status run_lstm_mx_step(aec_crn_handle* h, StreamState& ss, int l, in
 static hipError_t stream_cov_fill(aec_crn_handle* h, int first, int count, hipStream_t st) {
     const CancellerRows cr = crn_canceller_state_rows(h->cfg.nlms_taps, true);
     return aec::launch_stream_cov_fill(reinterpret_cast<float*>(h->ss->nstate) - aec::kStNlms, cr.floats(), first, count,
-                                       h->cfg.nlms_taps, h->kal_p0, st);
+                                       h->cfg.nlms_taps, h->canc.p0, st);
 }
 
 // the fused front's level table (stream_open checked the shapes: stream_enc_levels).  Its levels
@@ -752,11 +747,12 @@ static crn::StreamEncArgs stream_enc_args(aec_crn_handle* h, int B) {
     if (h->cfg.nlms_taps > 0) {
         ea.state = ss.nstate;
         ea.espec = ss.espec;
-        ea.mu = h->kalman ? h->kal_a : h->cfg.nlms_mu;
-        ea.beta = h->cfg.nlms_beta;
-        ea.delta = h->cfg.nlms_delta;
-        ea.p0 = h->kal_p0;
-        ea.kalman = h->kalman;
+        const aec::Canceller cc = h->canceller();
+        ea.mu = cc.gain;
+        ea.beta = cc.beta;
+        ea.delta = cc.delta;
+        ea.p0 = cc.p0;
+        ea.kalman = cc.kind;
     }
     ea.nlev = ss.enc_nlev;
     if (ss.enc_mx) {
@@ -789,7 +785,7 @@ static crn::StreamDecArgs stream_dec_args(aec_crn_handle* h, int B) {
 
 // a Kalman fused front that is not built (it would spill) takes the separate launches
 static bool kalman_front_built(const aec_crn_handle* h, bool mx4) {
-    return !(h->kalman && h->cfg.nlms_taps > 0 && !crn::stream_enc_kalman_ok(h->cfg.nlms_taps, mx4));
+    return !(h->canc.kind && h->cfg.nlms_taps > 0 && !crn::stream_enc_kalman_ok(h->cfg.nlms_taps, mx4));
 }
 
 template <typename T>
@@ -830,14 +826,7 @@ static aec_status stream_launches(aec_crn_handle* h, int par, const StreamIo& io
         ss.front_node[par] = last_node(st);
         ss.front_args[par] = fa;
         if (c.nlms_taps > 0) {
-            crn::StreamNlmsArgs na{ss.nrows, ss.nstate, ss.espec, bf.x0, B, c.nlms_mu, c.nlms_beta, c.nlms_delta};
-            if (h->kalman) {
-                crn::StreamKalmanArgs ka{na, h->kal_p0};
-                ka.mu = h->kal_a;
-                CRN_TRY(h, crn::launch_stream_kalman<T>(ka, c.nlms_taps, st));
-            } else {
-                CRN_TRY(h, crn::launch_stream_nlms<T>(na, c.nlms_taps, st));
-            }
+            CRN_TRY(h, crn::launch_stream_nlms<T>({ss.nrows, ss.nstate, ss.espec, bf.x0, B, h->canceller()}, st));
         }
     }
     aec_status s = run_encoder<T>(h, bf, B, st, first, false, &ss.sk);
@@ -1076,11 +1065,11 @@ aec_status aec_crn_set_canceller(aec_crn_handle* h, int32_t kind, float a, float
     bool unsupported = false;
     const std::string why = check_canceller(h->cfg.nlms_taps, kind, a, p0, h->ss != nullptr, &unsupported);
     if (!why.empty()) return crn_fail(h, unsupported ? AEC_ERR_UNSUPPORTED : AEC_ERR_INVALID_ARG, why);
-    if (kind == 1) {
-        h->kal_a = a;
-        h->kal_p0 = p0;
+    if (kind == aec::kCancellerKalman) {
+        h->canc.a = a;
+        h->canc.p0 = p0;
     }
-    h->kalman = kind;
+    h->canc.kind = kind;
     return AEC_OK;
 }
 
@@ -1141,9 +1130,9 @@ aec_status aec_crn_stream_open(aec_crn_handle* h, int32_t B) {
     CRN_TRY(h, alloc(&ss.tail, (size_t)B * 256 * sizeof(float)));
     if (h->cfg.nlms_taps > 0) {
         CRN_TRY(h, alloc(&ss.nrows, (size_t)B * 512 * sizeof(float2)));
-        const CancellerRows cr = crn_canceller_state_rows(h->cfg.nlms_taps, h->kalman != 0);
+        const CancellerRows cr = crn_canceller_state_rows(h->cfg.nlms_taps, h->canc.kind != 0);
         CRN_TRY(h, alloc(&ss.nstate, (size_t)B * cr.bytes()));
-        if (h->kalman) CRN_TRY(h, stream_cov_fill(h, 0, B, nullptr));
+        if (h->canc.kind) CRN_TRY(h, stream_cov_fill(h, 0, B, nullptr));
         CRN_TRY(h, alloc(&ss.espec, (size_t)B * 256 * sizeof(float2)));
     }
     // which fused kernels this handle's shapes admit (crn_plan.h), by AEC_CRN_STREAM_FUSE's bits
@@ -1221,10 +1210,10 @@ aec_status aec_crn_stream_reset(aec_crn_handle* h, int32_t b, void* stream) {
         CRN_TRY(h, hipMemsetAsync(ss.hop + ((size_t)q * ss.B + b0) * 256, 0, (size_t)nb * 256 * sizeof(float), st));
     CRN_TRY(h, hipMemsetAsync(ss.tail + (size_t)b0 * 256, 0, (size_t)nb * 256 * sizeof(float), st));
     if (ss.nstate) {   // a fresh recursion: W, history, power / psi = 0; Kalman: P = p0 again
-        const CancellerRows cr = crn_canceller_state_rows(h->cfg.nlms_taps, h->kalman != 0);
+        const CancellerRows cr = crn_canceller_state_rows(h->cfg.nlms_taps, h->canc.kind != 0);
         const size_t srow = (size_t)cr.rows * 256;
         CRN_TRY(h, hipMemsetAsync(ss.nstate + b0 * srow, 0, nb * srow * sizeof(float2), st));
-        if (h->kalman) {
+        if (h->canc.kind) {
             aec::DeviceGuard dg(h->device);
             if (dg.err != hipSuccess) return crn_fail(h, AEC_ERR_HIP, "hipSetDevice failed");
             CRN_TRY(h, stream_cov_fill(h, b0, nb, st));

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/aec_crn.h"
+#include "aec_canceller.h"
 #include "aec_knobs.h"
 
 namespace crn {
@@ -107,54 +108,11 @@ inline std::string check_cfg(const aec_crn_config& c) {
 // --------------------------------------------------------------------------
 // the linear stage's canceller (aec_crn_set_canceller) and its streaming state
 // --------------------------------------------------------------------------
-// One stream's canceller state of the per-hop step: rows of 256 float2 (bin slot k; slot 0 the
-// real pair of bins 0 and 256), in the order of the Little_net stream state's canceller block
-// (aec_host.h stream_state_floats, aec_launch.h): W[0 .. taps), the far-end history
-// R[t-1 .. t-taps+1], the NLMS power row (unused by the Kalman canceller), then for the Kalman
-// canceller the taps covariance rows P[0 .. taps) and one row psi.  -1: the kind has no such row.
-struct CancellerRows {
-    int w = 0;          // first of `taps` rows
-    int hist = 0;       // first of `nhist` = taps - 1 rows
-    int nhist = 0;
-    int power = 0;      // 2 taps - 1
-    int cov = -1;       // Kalman: first of `taps` rows (2 taps)
-    int psi = -1;       // Kalman: 3 taps
-    int rows = 0;       // rows per stream
-    int64_t floats() const { return (int64_t)rows * 512; }
-    size_t bytes() const { return (size_t)rows * 256 * 2 * sizeof(float); }
-};
-inline CancellerRows crn_canceller_state_rows(int taps, bool kalman) {
-    CancellerRows r;
-    if (taps <= 0) return r;
-    r.w = 0;
-    r.hist = taps;
-    r.nhist = taps - 1;
-    r.power = 2 * taps - 1;
-    r.rows = 2 * taps;
-    if (kalman) {
-        r.cov = 2 * taps;
-        r.psi = 3 * taps;
-        r.rows = 3 * taps + 1;
-    }
-    return r;
-}
-
-// aec_crn_set_canceller's argument rules (those of aec_set_canceller, aec_hip.h): "" or why the
-// call is refused; *unsupported set when the refusal is AEC_ERR_UNSUPPORTED, not _INVALID_ARG
-inline std::string check_canceller(int taps, int kind, float a, float p0, bool stream_open, bool* unsupported) {
-    *unsupported = false;
-    if (taps == 0) {
-        *unsupported = true;
-        return "no linear stage to select a canceller for (nlms_taps = 0)";
-    }
-    if (kind != 0 && kind != 1) return "canceller kind must be 0 (NLMS) or 1 (Kalman)";
-    if (stream_open) return "a streaming state is open: its layout depends on the canceller";
-    if (kind == 1) {
-        if (!(a > 0.f && a <= 1.f)) return "Kalman transition factor a must be in (0, 1]";
-        if (!(p0 >= 0.f && std::isfinite(p0))) return "Kalman initial covariance p0 must be finite and >= 0";
-    }
-    return "";
-}
+// One stream's canceller state of the per-hop step, and aec_crn_set_canceller's argument rules:
+// the Little_net path's own (aec_canceller.h)
+using aec::CancellerRows;
+using aec::check_canceller;
+inline CancellerRows crn_canceller_state_rows(int taps, bool kalman) { return aec::canceller_rows(taps, kalman); }
 
 inline size_t norm_count(const aec_crn_config& c, int ch) {
     return (c.version == 2 && c.use_cbn) ? 10 * (size_t)(ch / 2) : 4 * (size_t)ch;

@@ -582,55 +582,18 @@ __global__ __launch_bounds__(256) void crn_rows_x0_kernel(RowsX0Args p) {
     x0_bin<T>(row, k, e, fr);
 }
 
-// KALMAN: the canceller is aec::KalmanBin (p.mu carries its transition factor a; the state gains the
-// covariance rows and psi: crn_host.h crn_canceller_state_rows), else aec::NlmsBin
+// KALMAN: the canceller is aec::KalmanBin, else aec::NlmsBin; the whole bin restored from and saved
+// to the stream's rows (aec_frame.h bin_load / bin_store)
 template <typename T, int TAPS, bool KALMAN>
-__global__ __launch_bounds__(256) void crn_stream_nlms_kernel(
-    std::conditional_t<KALMAN, StreamKalmanArgs, StreamNlmsArgs> p) {
+__global__ __launch_bounds__(256) void crn_stream_nlms_kernel(StreamNlmsArgs p) {
     const int b = blockIdx.x, k = threadIdx.x;
-    float2* nst = p.state + (int64_t)b * (KALMAN ? 3 * TAPS + 1 : 2 * TAPS) * 256;
-    // restore (aec_stream.hip's layout: taps, raw far history, power); the
-    // history operands are re-derived with step()'s own expressions
-    std::conditional_t<KALMAN, aec::KalmanBin<TAPS>, aec::NlmsBin<TAPS>> nb;
-    if constexpr (KALMAN) nb.reset(k == 0, p.p0);
-    else nb.reset(k == 0);
-    float2 rh[TAPS > 1 ? TAPS - 1 : 1];
-#pragma unroll
-    for (int l = 0; l < TAPS; ++l) {
-        const float2 w = nst[l * 256 + k];
-        nb.w[l] = w;
-    }
-#pragma unroll
-    for (int l = 0; l + 1 < TAPS; ++l) {
-        const float2 r2 = nst[(TAPS + l) * 256 + k];
-        rh[l] = r2;
-        nb.hist(l, r2);
-    }
-    if constexpr (KALMAN) {
-#pragma unroll
-        for (int l = 0; l < TAPS; ++l) nb.pp[l] = nst[(2 * TAPS + l) * 256 + k];
-        nb.p = nst[3 * TAPS * 256 + k];
-    } else {
-        const float2 pp = nst[(2 * TAPS - 1) * 256 + k];
-        nb.p = pp;
-    }
+    float2* nst = p.state + (int64_t)b * aec::canceller_rows(TAPS, KALMAN).rows * 256;
+    aec::CancellerBin<TAPS, KALMAN> nb;
+    aec::bin_load(nb, nst, k, p.c.p0);
     const float2* rows = p.rows + (int64_t)b * 512;
     const float2 r = rows[256 + k];
-    const float2 e = nb.step(rows[k], r, p.mu, p.beta, p.delta);
-#pragma unroll
-    for (int l = 0; l < TAPS; ++l) nst[l * 256 + k] = nb.w[l];
-    if constexpr (TAPS > 1) {
-        nst[TAPS * 256 + k] = r;
-#pragma unroll
-        for (int l = 1; l + 1 < TAPS; ++l) nst[(TAPS + l) * 256 + k] = rh[l - 1];
-    }
-    if constexpr (KALMAN) {
-#pragma unroll
-        for (int l = 0; l < TAPS; ++l) nst[(2 * TAPS + l) * 256 + k] = nb.pp[l];
-        nst[3 * TAPS * 256 + k] = nb.p;
-    } else {
-        nst[(2 * TAPS - 1) * 256 + k] = nb.p;
-    }
+    const float2 e = nb.step(rows[k], r, p.c.gain, p.c.beta, p.c.delta);
+    aec::bin_store(nb, nst, k);
     float2* erow = p.espec + (int64_t)b * 256;
     erow[k] = e;
     // X0 bin k (k >= 1) or, on lane 0, the Nyquist bin: from this lane's own
@@ -678,36 +641,16 @@ template hipError_t launch_rows_x0<float>(const RowsX0Args&, hipStream_t);
 template hipError_t launch_rows_x0<bf16_t>(const RowsX0Args&, hipStream_t);
 
 template <typename T>
-hipError_t launch_stream_nlms(const StreamNlmsArgs& a, int taps, hipStream_t st) {
+hipError_t launch_stream_nlms(const StreamNlmsArgs& a, hipStream_t st) {
     if (a.B <= 0) return hipSuccess;
-    switch (taps) {
-#define CRN_NLMS_CASE(N) \
-        case N: hipLaunchKernelGGL((crn_stream_nlms_kernel<T, N, false>), dim3((unsigned)a.B), dim3(256), 0, st, a); break;
-        CRN_NLMS_CASE(1) CRN_NLMS_CASE(2) CRN_NLMS_CASE(3) CRN_NLMS_CASE(4)
-        CRN_NLMS_CASE(5) CRN_NLMS_CASE(6) CRN_NLMS_CASE(7) CRN_NLMS_CASE(8)
-#undef CRN_NLMS_CASE
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return aec::dispatch_canceller<1, 8>(a.c, hipErrorInvalidValue, [&](auto taps, auto kalman) {
+        hipLaunchKernelGGL((crn_stream_nlms_kernel<T, decltype(taps)::value, decltype(kalman)::value>),
+                           dim3((unsigned)a.B), dim3(256), 0, st, a);
+        return hipGetLastError();
+    });
 }
-template hipError_t launch_stream_nlms<float>(const StreamNlmsArgs&, int, hipStream_t);
-template hipError_t launch_stream_nlms<bf16_t>(const StreamNlmsArgs&, int, hipStream_t);
-
-template <typename T>
-hipError_t launch_stream_kalman(const StreamKalmanArgs& a, int taps, hipStream_t st) {
-    if (a.B <= 0) return hipSuccess;
-    switch (taps) {
-#define CRN_KALMAN_CASE(N) \
-        case N: hipLaunchKernelGGL((crn_stream_nlms_kernel<T, N, true>), dim3((unsigned)a.B), dim3(256), 0, st, a); break;
-        CRN_KALMAN_CASE(1) CRN_KALMAN_CASE(2) CRN_KALMAN_CASE(3) CRN_KALMAN_CASE(4)
-        CRN_KALMAN_CASE(5) CRN_KALMAN_CASE(6) CRN_KALMAN_CASE(7) CRN_KALMAN_CASE(8)
-#undef CRN_KALMAN_CASE
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-template hipError_t launch_stream_kalman<float>(const StreamKalmanArgs&, int, hipStream_t);
-template hipError_t launch_stream_kalman<bf16_t>(const StreamKalmanArgs&, int, hipStream_t);
+template hipError_t launch_stream_nlms<float>(const StreamNlmsArgs&, hipStream_t);
+template hipError_t launch_stream_nlms<bf16_t>(const StreamNlmsArgs&, hipStream_t);
 
 template <typename T>
 hipError_t launch_stream_front(const StreamFrontArgs& a, hipStream_t st) {

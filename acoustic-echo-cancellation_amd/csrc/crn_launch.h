@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "aec_canceller.h"
 #include "aec_knobs.h"
 #include "aec_tables.h"
 #include "crn_gemm.h"
@@ -96,23 +97,15 @@ struct StreamFrontArgs {
     float* save_mic = nullptr;  // non-null: copy the current hops into the ring ([B][256]) for the
     float* save_far = nullptr;  //   next call's frame and the back kernel
 };
-// NLMS streaming step: one block per stream, bin slot per lane; state
-// [B][2*TAPS][256] float2 (taps, far history r[t-1..t-TAPS+1], power — the
-// aec_stream.hip layout) -> E rows [B][256] and X0.
+// The canceller's streaming step (either kind, 1..8 taps): one block per stream, bin slot per lane;
+// state [B][rows][256] float2 (aec::canceller_rows) -> E rows [B][256] and X0.
 struct StreamNlmsArgs {
     const float2* rows;         // [B][2][256]
     float2* state;
     float2* espec;              // [B][256]
     void* x0;                   // [B][256][8]
     int32_t B;
-    float mu, beta, delta;
-};
-// The same step with the Kalman canceller (aec::KalmanBin; mu carries its transition factor a),
-// state [B][3*TAPS+1][256]: the NLMS rows (its power row unused), then the TAPS covariance rows
-// and psi (crn_host.h crn_canceller_state_rows).  A type of its own: the NLMS kernels keep
-// their argument block, so they compile to the code they were.
-struct StreamKalmanArgs : StreamNlmsArgs {
-    float p0 = 0.f;             // the initial covariance (KalmanBin::reset)
+    aec::Canceller c;
 };
 struct StreamBackArgs {
     const float* prev_mic;
@@ -154,14 +147,13 @@ struct StreamEncArgs {
     float* save_far;
     const aec::DevTables* tab;
     int32_t B;
-    float2* state;              // NLMS (taps > 0): [B][2 taps][256] (StreamNlmsArgs layout)
+    float2* state;              // taps > 0: [B][rows][256] (StreamNlmsArgs layout)
     float2* espec;              //   E rows [B][256]
     float mu, beta, delta;
     int32_t nlev;               // 3 or 4 (level 3: 16 output bins x 128 channels, K = 320)
     StreamEncLevel lev[4];
     StreamEncMxLevel mx4;       // mx4.wq non-null (nlev == 4): level 4 as well
-    // Kalman canceller (after every NLMS field: their offsets stay put): state is
-    // [B][3 taps + 1][256] (StreamNlmsArgs), mu carries a
+    // Kalman canceller (after every NLMS field: their offsets stay put): mu carries a
     float p0 = 0.f;
     int32_t kalman = 0;
 };
@@ -235,9 +227,7 @@ template <typename T>
 hipError_t launch_stream_front(const StreamFrontArgs& a, hipStream_t st);
 hipError_t launch_stream_back(const StreamBackArgs& a, int mode, hipStream_t st);
 template <typename T>
-hipError_t launch_stream_nlms(const StreamNlmsArgs& a, int taps, hipStream_t st);
-template <typename T>
-hipError_t launch_stream_kalman(const StreamKalmanArgs& a, int taps, hipStream_t st);
+hipError_t launch_stream_nlms(const StreamNlmsArgs& a, hipStream_t st);
 template <typename T>
 hipError_t launch_rows_x0(const RowsX0Args& a, hipStream_t st);
 hipError_t launch_unpack_rows(const float2* espec, const int64_t* lens, int B, int64_t Tmax, float2* spec,

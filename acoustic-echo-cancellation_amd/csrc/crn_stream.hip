@@ -81,20 +81,14 @@ hipError_t launch_stream_enc(const StreamEncArgs& a, int taps, hipStream_t st) {
             return hipErrorInvalidValue;
     }
     if (a.kalman) return launch_stream_enc_kalman(a, taps, st);   // crn_stream_kalman.hip (arguments checked above)
-    switch (taps) {
-#define CRN_ENC_CASE(N)                                                                               \
-    case N:                                                                                           \
-        if (a.mx4.wq)                                                                                 \
-            hipLaunchKernelGGL((crn_stream_enc_kernel<N, true, false>), dim3((unsigned)a.B), dim3(256), 0, st, a); \
-        else                                                                                          \
-            hipLaunchKernelGGL((crn_stream_enc_kernel<N, false, false>), dim3((unsigned)a.B), dim3(256), 0, st, a); \
-        break;
-        CRN_ENC_CASE(0) CRN_ENC_CASE(1) CRN_ENC_CASE(2) CRN_ENC_CASE(3) CRN_ENC_CASE(4)
-        CRN_ENC_CASE(5) CRN_ENC_CASE(6) CRN_ENC_CASE(7) CRN_ENC_CASE(8)
-#undef CRN_ENC_CASE
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return aec::dispatch_taps<0, 8>(taps, hipErrorInvalidValue, [&](auto t) {
+        constexpr int N = decltype(t)::value;
+        if (a.mx4.wq)
+            hipLaunchKernelGGL((crn_stream_enc_kernel<N, true, false>), dim3((unsigned)a.B), dim3(256), 0, st, a);
+        else
+            hipLaunchKernelGGL((crn_stream_enc_kernel<N, false, false>), dim3((unsigned)a.B), dim3(256), 0, st, a);
+        return hipGetLastError();
+    });
 }
 
 // --------------------------------------------------------------------------

@@ -203,7 +203,7 @@ __device__ __forceinline__ void x0_put(bf16_t* x0, int k, float2 m, float2 f) {
 // a separate instantiation: at many streams per CU its occupancy, not the extra launch, decides;
 // without the fold and with <= 4 taps it fits 2 waves per SIMD with no scratch)
 // KALMAN: the canceller step is aec::KalmanBin's (p.mu carries a; the state rows gain the covariances
-// and psi: crn_host.h crn_canceller_state_rows).  The kernel itself is templated, not a shared
+// and psi: aec_canceller.h canceller_rows).  The kernel itself is templated, not a shared
 // __device__ body, so the NLMS instantiations stay the code they were.
 // Launch bounds: the Kalman state is 2 VGPRs per tap more than the NLMS state, and <4, false, true>
 // at 2 waves per SIMD spilled 52 B per lane: its limit is 3 taps (profiles/crn_kalman_canceller.txt).
@@ -245,27 +245,28 @@ __global__ __launch_bounds__(256, MX4 || TAPS > (KALMAN ? 3 : 4) ? 1 : 2) void c
     const float2 t0 = p.tab->twT[tid], t1 = p.tab->tw512[tid];
     const float2 t2 = tid < 2 ? p.tab->tw512[256 + tid] : make_float2(0.f, 0.f);
     const float h0 = p.tab->hann[tid], h1 = p.tab->hann[tid + 256];
-    std::conditional_t<KALMAN, aec::KalmanBin<(TAPS > 0 ? TAPS : 1)>, aec::NlmsBin<(TAPS > 0 ? TAPS : 1)>> nb;
+    constexpr aec::CancellerRows R = aec::canceller_rows(TAPS, KALMAN);
+    aec::CancellerBin<TAPS, KALMAN> nb;
     float2 rh[TAPS > 1 ? TAPS - 1 : 1];
     float2* nst = nullptr;
     if constexpr (TAPS > 0) {
         const int k = tid;
-        nst = p.state + (int64_t)b * (KALMAN ? 3 * TAPS + 1 : 2 * TAPS) * 256;
+        nst = p.state + (int64_t)b * R.rows * 256;
         if constexpr (KALMAN) nb.reset(k == 0, p.p0);
         else nb.reset(k == 0);
 #pragma unroll
         for (int l = 0; l < TAPS; ++l) {
-            const float2 w = nst[l * 256 + k];
+            const float2 w = nst[(R.w + l) * 256 + k];
             nb.w[l] = w;
         }
 #pragma unroll
-        for (int l = 0; l + 1 < TAPS; ++l) rh[l] = nst[(TAPS + l) * 256 + k];
+        for (int l = 0; l + 1 < TAPS; ++l) rh[l] = nst[(R.hist + l) * 256 + k];
         if constexpr (KALMAN) {
 #pragma unroll
-            for (int l = 0; l < TAPS; ++l) nb.pp[l] = nst[(2 * TAPS + l) * 256 + k];
-            nb.p = nst[3 * TAPS * 256 + k];
+            for (int l = 0; l < TAPS; ++l) nb.pp[l] = nst[(R.cov + l) * 256 + k];
+            nb.p = nst[R.psi * 256 + k];
         } else {
-            const float2 pp = nst[(2 * TAPS - 1) * 256 + k];
+            const float2 pp = nst[R.power * 256 + k];
             nb.p = pp;
         }
     }
@@ -346,18 +347,18 @@ __global__ __launch_bounds__(256, MX4 || TAPS > (KALMAN ? 3 : 4) ? 1 : 2) void c
             for (int l = 0; l + 1 < TAPS; ++l) nb.hist(l, rh[l]);
             e = nb.step(rm, rf, p.mu, p.beta, p.delta);
 #pragma unroll
-            for (int l = 0; l < TAPS; ++l) nst[l * 256 + k] = nb.w[l];
+            for (int l = 0; l < TAPS; ++l) nst[(R.w + l) * 256 + k] = nb.w[l];
             if constexpr (TAPS > 1) {
-                nst[TAPS * 256 + k] = rf;
+                nst[R.hist * 256 + k] = rf;
 #pragma unroll
-                for (int l = 1; l + 1 < TAPS; ++l) nst[(TAPS + l) * 256 + k] = rh[l - 1];
+                for (int l = 1; l + 1 < TAPS; ++l) nst[(R.hist + l) * 256 + k] = rh[l - 1];
             }
             if constexpr (KALMAN) {
 #pragma unroll
-                for (int l = 0; l < TAPS; ++l) nst[(2 * TAPS + l) * 256 + k] = nb.pp[l];
-                nst[3 * TAPS * 256 + k] = nb.p;
+                for (int l = 0; l < TAPS; ++l) nst[(R.cov + l) * 256 + k] = nb.pp[l];
+                nst[R.psi * 256 + k] = nb.p;
             } else {
-                nst[(2 * TAPS - 1) * 256 + k] = nb.p;
+                nst[R.power * 256 + k] = nb.p;
             }
             p.espec[(int64_t)b * 256 + k] = e;
         }

@@ -25,20 +25,14 @@ bool stream_enc_kalman_ok(int taps, bool mx4) {
 hipError_t launch_stream_enc_kalman(const StreamEncArgs& a, int taps, hipStream_t st) {
     if (a.B <= 0) return hipSuccess;
     if (!a.kalman || !a.state || !a.espec || !stream_enc_kalman_ok(taps, a.mx4.wq != nullptr)) return hipErrorInvalidValue;
-    switch (taps) {
-#define CRN_ENC_CASE(N)                                                                               \
-    case N:                                                                                           \
-        if (a.mx4.wq)                                                                                 \
-            hipLaunchKernelGGL((crn_stream_enc_kernel<N, true, true>), dim3((unsigned)a.B), dim3(256), 0, st, a); \
-        else                                                                                          \
-            hipLaunchKernelGGL((crn_stream_enc_kernel<N, false, true>), dim3((unsigned)a.B), dim3(256), 0, st, a); \
-        break;
-        CRN_ENC_CASE(1) CRN_ENC_CASE(2) CRN_ENC_CASE(3) CRN_ENC_CASE(4)
-        CRN_ENC_CASE(5) CRN_ENC_CASE(6) CRN_ENC_CASE(7) CRN_ENC_CASE(8)
-#undef CRN_ENC_CASE
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return aec::dispatch_taps<1, 8>(taps, hipErrorInvalidValue, [&](auto t) {
+        constexpr int N = decltype(t)::value;
+        if (a.mx4.wq)
+            hipLaunchKernelGGL((crn_stream_enc_kernel<N, true, true>), dim3((unsigned)a.B), dim3(256), 0, st, a);
+        else
+            hipLaunchKernelGGL((crn_stream_enc_kernel<N, false, true>), dim3((unsigned)a.B), dim3(256), 0, st, a);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace crn
