@@ -27,7 +27,7 @@ EXPORTS = ('aec_weights_count', 'aec_create', 'aec_set_weights', 'aec_set_erb', 
            'aec_process_siglens',
            'aec_prepare', 'aec_prepare_siglens', 'aec_process_prepared',
            'aec_stream_open', 'aec_stream_reset', 'aec_stream_step', 'aec_stream_push',
-           'aec_delay_estimate', 'aec_delay_apply',
+           'aec_delay_estimate', 'aec_delay_apply', 'aec_drift_estimate', 'aec_drift_apply',
            'aec_delay_track_open', 'aec_delay_track_reset', 'aec_delay_track_push',
            'aec_set_debug', 'aec_debug_copy', 'aec_profile_enable', 'aec_profile_read',
            'aec_erb_tables_check', 'aec_num_frames', 'aec_out_len', 'aec_last_error', 'aec_destroy',
@@ -120,6 +120,12 @@ def load():
         lib.aec_delay_estimate.restype = ctypes.c_int
         lib.aec_delay_apply.argtypes = [P, P, P, ctypes.c_int32, ctypes.c_int64, P, P, ctypes.c_int64, P]
         lib.aec_delay_apply.restype = ctypes.c_int
+    if LIB_PATH == _DEFAULT_LIB or hasattr(lib, 'aec_drift_estimate'):   # absent from an older A/B build
+        lib.aec_drift_estimate.argtypes = [P, P, P, P, ctypes.c_int32, ctypes.c_int64, P, ctypes.c_int32, ctypes.c_float,
+                                           ctypes.c_int32, P, P, P]
+        lib.aec_drift_estimate.restype = ctypes.c_int
+        lib.aec_drift_apply.argtypes = [P, P, P, ctypes.c_int32, ctypes.c_int64, P, P, P, ctypes.c_int64, P]
+        lib.aec_drift_apply.restype = ctypes.c_int
     if LIB_PATH == _DEFAULT_LIB or hasattr(lib, 'aec_delay_track_open'):   # absent from an older A/B build
         lib.aec_delay_track_open.argtypes = [P, ctypes.c_int32, ctypes.POINTER(DelayTrackConfig)]
         lib.aec_delay_track_open.restype = ctypes.c_int
@@ -329,6 +335,24 @@ class Handle:
         lens = np.ascontiguousarray(lengths, dtype=np.int64)
         check(self.lib.aec_delay_apply(self.h, ref_ptr, lens.ctypes.data, int(B), int(ld), shift_ptr, out_ptr,
                                        int(ld_out), stream), self.h, 'aec_delay_apply')
+
+    def drift_estimate(self, mic_ptr, ref_ptr, lengths, B, ld, shift_ptr, seg_frames, max_ppm, ngrid, ppm_ptr, curve_ptr,
+                       stream):
+        """lengths: host [B]; shift_ptr: device [B] int32 frames or None; ppm_ptr: device [B] float32;
+        curve_ptr: device [B, ngrid] or None"""
+        import numpy as np
+        lens = np.ascontiguousarray(lengths, dtype=np.int64)
+        check(self.lib.aec_drift_estimate(self.h, mic_ptr, ref_ptr, lens.ctypes.data, int(B), int(ld), shift_ptr,
+                                          int(seg_frames), float(max_ppm), int(ngrid), ppm_ptr, curve_ptr, stream),
+              self.h, 'aec_drift_estimate')
+
+    def drift_apply(self, ref_ptr, lengths, B, ld, shift_ptr, ppm_ptr, out_ptr, ld_out, stream):
+        """shift_ptr: device [B] int32 frames or None; ppm_ptr: device [B] float32 (clamped to +-2000 by
+        the kernel, NaN counts as 0)"""
+        import numpy as np
+        lens = np.ascontiguousarray(lengths, dtype=np.int64)
+        check(self.lib.aec_drift_apply(self.h, ref_ptr, lens.ctypes.data, int(B), int(ld), shift_ptr, ppm_ptr, out_ptr,
+                                       int(ld_out), stream), self.h, 'aec_drift_apply')
 
     def delay_track_open(self, B, max_lag, forget, period, hold, ratio, lead):
         cfg = DelayTrackConfig(int(max_lag), int(period), int(hold), int(lead), float(forget), float(ratio))

@@ -34,6 +34,10 @@ Extra flags (all optional):
 - `--align MAX_LAG` estimates each utterance's far-end bulk delay over lags of
   0 .. MAX_LAG frames and feeds the canceller the reference delayed by it
   (`aec_amd.delay`; off by default);
+- `--drift MAX_PPM` estimates each utterance's far-end clock drift within
+  +-MAX_PPM and feeds the canceller the reference resampled by it, delayed by
+  `--align`'s estimate in the same pass when both are given (`aec_amd.drift`;
+  off by default);
 - `--streams` sets the utterances per GPU call;
 - `--device` picks the GPU (default: LOCAL_RANK, the rank's bound GPU);
 - `--gather` writes every file on rank 0 (waveforms gathered over RCCL).
@@ -89,6 +93,9 @@ def build_parser():
     p.add_argument('--align', type=int, default=None, metavar='MAX_LAG',
                    help='estimate the far-end bulk delay per utterance (lags 0..MAX_LAG frames, at most 63) and '
                         'feed the aligned reference; off when not given')
+    p.add_argument('--drift', type=float, default=None, metavar='MAX_PPM',
+                   help='estimate the far-end clock drift per utterance (within +-MAX_PPM, at most 2000) and feed the '
+                        'resampled reference, with --align delayed by that estimate too; off when not given')
     p.add_argument('--streams', type=int, default=64, help='utterances per GPU call')
     p.add_argument('--device', type=int, default=None, help='GPU index (default: LOCAL_RANK or 0)')
     p.add_argument('--gather', action='store_true',
@@ -147,14 +154,21 @@ class Tester(object):
         align = getattr(self.args, 'align', None)
         if align is not None:
             from .delay import align_ref, estimate_delay
+        drift = getattr(self.args, 'drift', None)
+        if drift is not None:
+            from .drift import estimate_drift, resample_ref
 
         def enhance(mic, ref, near, lengths):
             lengths = np.asarray(lengths, np.int64).reshape(len(mic), 3)
             with torch.no_grad():
                 M, R, N = (torch.from_numpy(a).to(device, non_blocking=True) for a in (mic, ref, near))
-                if align is not None:
-                    # the overlap of mic and ref bounds the search; the shifted reference keeps its length
-                    both = np.minimum(lengths[:, 0], lengths[:, 1])
+                # the overlap of mic and ref bounds either search; the reference keeps its length
+                both = np.minimum(lengths[:, 0], lengths[:, 1])
+                if drift is not None:
+                    d = estimate_delay(M, R, both, max_lag=align) if align is not None else None
+                    ppm = estimate_drift(M, R, both, delay=d, max_ppm=drift)
+                    R = resample_ref(R, lengths[:, 1], ppm, delay=d)
+                elif align is not None:
                     R = align_ref(R, lengths[:, 1], estimate_delay(M, R, both, max_lag=align))
                 out, _ = net.forward_ragged(M, R, N, erb, lengths)
                 out = out.cpu().numpy()

@@ -18,6 +18,7 @@
 
 #include "../../include/aec_hip.h"
 #include "aec_delay.h"
+#include "aec_drift.h"
 #include "aec_device.h"
 #include "aec_host.h"
 #include "aec_launch.h"
@@ -120,6 +121,7 @@ struct aec_handle {
     int64_t stream_stride = 0;
     // streaming delay tracker (aec_delay_track_*): per-stream state [track_B][track_stride]
     float* d_track = nullptr;
+    float* d_drift_tab = nullptr;   // the resampler's interpolation table (aec_drift.h build_drift_table)
     int32_t track_B = 0;
     int64_t track_stride = 0;
     aec_delay_track_config track_cfg{};
@@ -316,6 +318,12 @@ aec_status aec_create(const aec_config* cfg, const float* weights, size_t n_weig
     DevTables tab;
     build_dev_tables(tab);
     if (hipMemcpy(h->d_tab, &tab, sizeof(tab), hipMemcpyHostToDevice) != hipSuccess) return bail(AEC_ERR_HIP);
+    {
+        const std::vector<float> dt = build_drift_table();
+        if (hipMalloc(&h->d_drift_tab, dt.size() * sizeof(float)) != hipSuccess) return bail(AEC_ERR_OOM);
+        if (hipMemcpy(h->d_drift_tab, dt.data(), dt.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+            return bail(AEC_ERR_HIP);
+    }
     if (weights && aec_set_weights(h, weights, n_weights) != AEC_OK) return bail(AEC_ERR_INVALID_ARG);
     if (erb) {
         const aec_status s = aec_set_erb(h, erb);
@@ -1049,6 +1057,54 @@ aec_status aec_delay_apply(aec_handle* h, const float* ref, const int64_t* lengt
     return AEC_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Far-end clock drift (kernels in aec_drift.hip, checks in aec_host.h).  Stateless as the delay
+// calls above, with the same launches of kDelayRows rows; the resampler's table is the handle's
+// one piece of it, uploaded by aec_create.
+// ---------------------------------------------------------------------------
+static_assert(kDriftRows == kDelayRows, "one cut of a batch into launches for both");
+
+aec_status aec_drift_estimate(aec_handle* h, const float* mic, const float* ref, const int64_t* lengths, int32_t B,
+                              int64_t ld, const int32_t* shift, int32_t seg_frames, float max_ppm, int32_t ngrid,
+                              float* drift_ppm, float* curve, void* stream) {
+    if (!h) return AEC_ERR_INVALID_ARG;
+    const Check c = check_drift_args(true, mic, ref, drift_ppm, lengths, B, ld, seg_frames, max_ppm, ngrid, 0);
+    if (c.status != AEC_OK) return fail(h, c.status, c.why);
+    AEC_ON_DEVICE(h);
+    DriftEstArgs a{};
+    a.mic = mic; a.ref = ref; a.ld = ld; a.shift = shift; a.tables = reinterpret_cast<const float*>(h->d_tab);
+    a.drift_ppm = drift_ppm; a.curve = curve; a.seg_frames = seg_frames; a.ngrid = ngrid; a.max_ppm = max_ppm;
+    for (int32_t b0 = 0; b0 < B; b0 += kDriftRows) {
+        const int nb = std::min<int32_t>(kDriftRows, B - b0);
+        a.b0 = b0;
+        for (int i = 0; i < nb; ++i) a.len[i] = (int32_t)lengths[b0 + i];
+        HIP_TRY(h, launch_drift_estimate(a, nb, reinterpret_cast<hipStream_t>(stream)));
+    }
+    return AEC_OK;
+}
+
+aec_status aec_drift_apply(aec_handle* h, const float* ref, const int64_t* lengths, int32_t B, int64_t ld,
+                           const int32_t* shift, const float* drift_ppm, float* out, int64_t ld_out, void* stream) {
+    if (!h) return AEC_ERR_INVALID_ARG;
+    const Check c = check_drift_args(false, ref, drift_ppm, out, lengths, B, ld, 0, 0.f, 0, ld_out);
+    if (c.status != AEC_OK) return fail(h, c.status, c.why);
+    AEC_ON_DEVICE(h);
+    DriftApplyArgs a{};
+    a.ref = ref; a.ld = ld; a.shift = shift; a.drift_ppm = drift_ppm; a.table = h->d_drift_tab;
+    a.out = out; a.ld_out = ld_out;
+    for (int32_t b0 = 0; b0 < B; b0 += kDriftRows) {
+        const int nb = std::min<int32_t>(kDriftRows, B - b0);
+        a.b0 = b0;
+        int64_t nmax = 0;
+        for (int i = 0; i < nb; ++i) {
+            a.len[i] = (int32_t)lengths[b0 + i];
+            nmax = std::max(nmax, lengths[b0 + i]);
+        }
+        HIP_TRY(h, launch_drift_apply(a, nb, nmax, reinterpret_cast<hipStream_t>(stream)));
+    }
+    return AEC_OK;
+}
+
 void aec_destroy(aec_handle* h) {
     if (!h) return;
     for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
@@ -1072,7 +1128,7 @@ void aec_destroy(aec_handle* h) {
     (void)hipFree(h->d_mom); (void)hipFree(h->d_cvals); (void)hipFree(h->d_lists);
     (void)hipFree(h->d_feats); (void)hipFree(h->d_est); (void)hipFree(h->d_dbg); (void)hipFree(h->d_spec);
     (void)hipFree(h->d_state); (void)hipFree(h->d_rows); (void)hipFree(h->d_progress);
-    (void)hipFree(h->d_track);
+    (void)hipFree(h->d_track); (void)hipFree(h->d_drift_tab);
     if (h->h_pipe_err) (void)hipHostFree(h->h_pipe_err);
     (void)hipFree(h->d_th); (void)hipFree(h->d_tloss); (void)hipFree(h->d_rec); (void)hipFree(h->d_dg);
     (void)hipFree(h->d_part); (void)hipFree(h->d_scan);

@@ -14,6 +14,7 @@
 
 #include "../../include/aec_hip.h"
 #include "aec_canceller.h"
+#include "aec_drift.h"
 
 namespace aec {
 
@@ -297,6 +298,40 @@ inline Check check_delay_args(bool estimate, const void* in0, const void* in1, c
     if (!estimate) {
         if (ld_out < m) return {AEC_ERR_INVALID_ARG, "ld_out below the longest length"};
         if (out == in0) return {AEC_ERR_INVALID_ARG, "out must not be ref (the shift cannot run in place)"};
+    }
+    if (nmax) *nmax = m;
+    return {};
+}
+
+// aec_drift_estimate (estimate = true: in0 = mic, in1 = ref, out = drift_ppm; seg_frames in
+// [4, 64], max_ppm in (0, 2000], ngrid odd in [3, 255]) and aec_drift_apply (in0 = ref, in1 =
+// drift_ppm, out = the resampled rows; ld_out must hold the longest row, and the resampler cannot
+// run in place).  The shift is optional in both and is no argument here.  Lengths as for the
+// delay calls, with the same limit: the kernels address a row through 32-bit byte offsets.
+inline Check check_drift_args(bool estimate, const void* in0, const void* in1, const void* out, const int64_t* lengths,
+                              int32_t B, int64_t ld, int32_t seg_frames, float max_ppm, int32_t ngrid, int64_t ld_out,
+                              int64_t* nmax = nullptr) {
+    if (!in0 || !in1 || !out)
+        return {AEC_ERR_INVALID_ARG, estimate ? "null mic / ref / drift_ppm" : "null ref / drift_ppm / out"};
+    if (!lengths) return {AEC_ERR_INVALID_ARG, "null lengths"};
+    if (B < 1) return {AEC_ERR_INVALID_ARG, "B must be >= 1"};
+    if (estimate) {
+        if (seg_frames < kDriftSegMin || seg_frames > kDriftSegMax)
+            return {AEC_ERR_INVALID_ARG, "seg_frames out of [4, 64]"};
+        if (!(max_ppm > 0.f && max_ppm <= kDriftMaxPpm)) return {AEC_ERR_INVALID_ARG, "max_ppm out of (0, 2000]"};
+        if (ngrid < kDriftGridMin || ngrid > kDriftGridMax || ngrid % 2 == 0)
+            return {AEC_ERR_INVALID_ARG, "ngrid must be odd, in [3, 255]"};
+    }
+    int64_t m = 0;
+    for (int b = 0; b < B; ++b) {
+        const int64_t n = lengths[b];
+        if (n < 1 || n > ld) return {AEC_ERR_INVALID_ARG, "length out of [1, ld]"};
+        if (n > kDelayMaxLen) return {AEC_ERR_UNSUPPORTED, "stream longer than 2^29 - 4096 samples"};
+        m = n > m ? n : m;
+    }
+    if (!estimate) {
+        if (ld_out < m) return {AEC_ERR_INVALID_ARG, "ld_out below the longest length"};
+        if (out == in0) return {AEC_ERR_INVALID_ARG, "out must not be ref (the resampler cannot run in place)"};
     }
     if (nmax) *nmax = m;
     return {};

@@ -243,6 +243,65 @@ aec_status aec_delay_estimate(aec_handle* h, const float* mic, const float* ref,
 aec_status aec_delay_apply(aec_handle* h, const float* ref, const int64_t* lengths, int32_t B, int64_t ld,
                            const int32_t* shift, float* out, int64_t ld_out, void* stream);
 
+/* Far-end clock drift (no reference counterpart).  Play-out and
+ * capture run on different crystals, 50 .. 500 ppm apart on USB and Bluetooth
+ * devices, so ref is a slowly stretched copy of what the loudspeaker played and
+ * the per-bin filters chase a phase that keeps rotating.  aec_drift_estimate
+ * finds the stretch, aec_drift_apply resamples ref by it (and delays it by the
+ * bulk delay in the same pass), and the canceller runs unchanged on the result.
+ * Sign: positive ppm means the reference runs fast, ref[i] = played(i (1 + eps)),
+ * eps = ppm 1e-6.
+ *
+ * aec_drift_estimate.  Frames as in aec_delay_estimate (Hann window, no
+ * normaliser, T = n/256 + 1), bins k = 1..255, R[t] = 0 for t < 0, s_b =
+ * shift[b] clamped to [0, 64] (0 when shift is NULL), S = seg_frames,
+ * ns = T / S segments; frames past ns S are ignored:
+ *   C_s[k] = sum_{t in segment s} M[t,k] conj(R[t - s_b, k])
+ *   Z_s    = C_s conj(C_{s-1})                          s = 1 .. ns-1
+ *   D[k]   = sum_s Z_s / sqrt(|Z_s|^2 + 1e-30)
+ *   J[g]   = sum_k Re(D[k] exp(+j 2 pi k eps_g 256 S / 512))
+ *   eps_g  = (g - G) (max_ppm / G) 1e-6,  G = (ngrid - 1) / 2,  g = 0 .. ngrid-1
+ *   drift  = ppm of the first maximiser of J, plus a parabolic offset through
+ *            its two neighbours (only at an interior maximum with negative
+ *            curvature; clamped to half a grid step)
+ * and 0 when ns < 2 or the curve is all zero.  The product of adjacent segments'
+ * cross-spectra cancels the room response, which they share; what is left is the
+ * lag step eps 256 S between them.  The normalisation per pair keeps loud
+ * segments from deciding alone.
+ *   mic, ref  : device [B, ld] float32
+ *   lengths   : host [B] int64, each in [1, ld] (and at most 2^29 - 4096:
+ *               AEC_ERR_UNSUPPORTED beyond)
+ *   shift     : DEVICE [B] int32 frames, or NULL
+ *   seg_frames: 4 .. 64;  max_ppm: (0, 2000];  ngrid: odd, 3 .. 255
+ *   drift_ppm : device [B] float32
+ *   curve     : device [B, ngrid] float32 receives J, or NULL
+ *
+ * aec_drift_apply.  q = 1 / (1 + (double)ppm_b 1e-6), ppm_b = drift_ppm[b]
+ * clamped to +-2000, NaN counting as 0.  For i < lengths[b], in float64 up to fr:
+ *   p  = (double)i q - 256 s_b      i0 = floor(p)       fr = (float)(p - i0)
+ *   u  = 256 fr                     ph = min((int)u, 255)       a = u - ph
+ *   out[b, i] = sum_{j=-15}^{16} ref[b, i0 + j] ((1 - a) h[ph][j] + a h[ph+1][j])
+ * ref reads as 0 outside [0, lengths[b]); nothing is written beyond lengths[b].
+ * h[ph][j] = sinc(j - ph/256) w(j - ph/256) for ph = 0..256, w(t) =
+ * I0(9 sqrt(1 - (t/16)^2)) / I0(9) for |t| < 16, else 0 (32 taps under a Kaiser
+ * window, beta 9), built in float64 and rounded to float32.  h[0] is exactly the
+ * unit impulse: ppm 0 returns ref, and ppm 0 with a shift aec_delay_apply's output.
+ *   drift_ppm : DEVICE [B] float32 (e.g. aec_drift_estimate's, so a caller need
+ *               not synchronise between the two calls)
+ *   out       : device [B, ld_out] float32, ld_out >= the longest length; not ref
+ * Both calls run on a bare handle (no weights, no ERB matrix), queue on the given
+ * stream and never synchronise, touch no streaming, training or look-ahead state,
+ * and cut a batch into launches of 256 rows with the host lengths in the kernel
+ * arguments.  A stream's result does not depend on B, on its row or on the other
+ * rows.  AEC_ERR_INVALID_ARG (text in aec_last_error): a null pointer (shift and
+ * curve excepted), B < 1, a length outside [1, ld], seg_frames, max_ppm or ngrid
+ * outside its range, ld_out below the longest length, out == ref. */
+aec_status aec_drift_estimate(aec_handle* h, const float* mic, const float* ref, const int64_t* lengths,
+                              int32_t B, int64_t ld, const int32_t* shift, int32_t seg_frames, float max_ppm,
+                              int32_t ngrid, float* drift_ppm, float* curve, void* stream);
+aec_status aec_drift_apply(aec_handle* h, const float* ref, const int64_t* lengths, int32_t B, int64_t ld,
+                           const int32_t* shift, const float* drift_ppm, float* out, int64_t ld_out, void* stream);
+
 /* The far-end delay while streaming (no reference counterpart): the
  * streaming counterpart of aec_delay_estimate / aec_delay_apply, with
  * aec_stream_push's contract.  Its state lives on the device, a call advances
