@@ -8,6 +8,7 @@ Public surface (mirrors the reference):
   * ``estimate_delay`` / ``align_ref``              build-defined far-end bulk-delay compensation (batch path)
   * ``estimate_drift`` / ``resample_ref``           build-defined far-end clock-drift compensation (batch path)
   * ``DelayTracker(B, device, ...)``                build-defined far-end delay tracking ahead of ``stream_push``
+  * ``DriftTracker(B, device, ...)``                build-defined far-end clock-drift tracking ahead of ``DelayTracker``
   * ``dccrn.DCCRN(config)`` / ``dccrn2.DCCRN(config)`` scripts/network/dccrn.py:453, dccrn2.py:10 (CRN, eval)
 The compute runs in ``libaec_hip.so`` (C ABI: include/aec_hip.h, include/aec_crn.h).
 """
@@ -15,7 +16,7 @@ from .configs import speech_conf, erb_conf, train_conf, nlms_conf, kalman_conf, 
 from .erb import EquivalentRectangularBandwidth, erb_matrix     # noqa: F401
 from .little_net import Little_net                              # noqa: F401
 from .delay import estimate_delay, align_ref, DelayTracker      # noqa: F401  (far-end bulk delay)
-from .drift import estimate_drift, resample_ref                 # noqa: F401  (far-end clock drift)
+from .drift import estimate_drift, resample_ref, DriftTracker   # noqa: F401  (far-end clock drift)
 from . import dccrn, dccrn2                                     # noqa: F401  (DCCRN v1 / v2 drop-ins)
 
 WIN_SIZE = 512

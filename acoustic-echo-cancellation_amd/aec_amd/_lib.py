@@ -29,6 +29,7 @@ EXPORTS = ('aec_weights_count', 'aec_create', 'aec_set_weights', 'aec_set_erb', 
            'aec_stream_open', 'aec_stream_reset', 'aec_stream_step', 'aec_stream_push',
            'aec_delay_estimate', 'aec_delay_apply', 'aec_drift_estimate', 'aec_drift_apply',
            'aec_delay_track_open', 'aec_delay_track_reset', 'aec_delay_track_push',
+           'aec_drift_track_open', 'aec_drift_track_reset', 'aec_drift_track_push',
            'aec_set_debug', 'aec_debug_copy', 'aec_profile_enable', 'aec_profile_read',
            'aec_erb_tables_check', 'aec_num_frames', 'aec_out_len', 'aec_last_error', 'aec_destroy',
            'aec_set_weights_device', 'aec_train_forward', 'aec_train_backward', 'aec_train_generation',
@@ -57,6 +58,13 @@ class DelayTrackConfig(ctypes.Structure):
     """aec_delay_track_config (include/aec_hip.h)."""
     _fields_ = [('max_lag', ctypes.c_int32), ('period', ctypes.c_int32), ('hold', ctypes.c_int32),
                 ('lead', ctypes.c_int32), ('forget', ctypes.c_float), ('ratio', ctypes.c_float)]
+
+
+class DriftTrackConfig(ctypes.Structure):
+    """aec_drift_track_config (include/aec_hip.h)."""
+    _fields_ = [('seg_frames', ctypes.c_int32), ('pairs', ctypes.c_int32), ('ngrid', ctypes.c_int32),
+                ('latency', ctypes.c_int32), ('gain', ctypes.c_float), ('max_ppm', ctypes.c_float),
+                ('init_ppm', ctypes.c_float)]
 
 
 class AecConfig(ctypes.Structure):
@@ -133,6 +141,13 @@ def load():
         lib.aec_delay_track_reset.restype = ctypes.c_int
         lib.aec_delay_track_push.argtypes = [P, P, P, ctypes.c_int64, P, ctypes.c_int64, P, ctypes.c_int32, P, P, P]
         lib.aec_delay_track_push.restype = ctypes.c_int
+    if LIB_PATH == _DEFAULT_LIB or hasattr(lib, 'aec_drift_track_open'):   # absent from an older A/B build
+        lib.aec_drift_track_open.argtypes = [P, ctypes.c_int32, ctypes.POINTER(DriftTrackConfig)]
+        lib.aec_drift_track_open.restype = ctypes.c_int
+        lib.aec_drift_track_reset.argtypes = [P, ctypes.c_int32, P]
+        lib.aec_drift_track_reset.restype = ctypes.c_int
+        lib.aec_drift_track_push.argtypes = [P, P, P, ctypes.c_int64, P, ctypes.c_int64, P, ctypes.c_int32, P, P, P, P, P]
+        lib.aec_drift_track_push.restype = ctypes.c_int
     lib.aec_set_debug.argtypes = [P, ctypes.c_int32]
     lib.aec_set_debug.restype = ctypes.c_int
     lib.aec_debug_copy.argtypes = [P, ctypes.c_int32, P, ctypes.c_size_t, P]
@@ -368,6 +383,22 @@ class Handle:
         check(self.lib.aec_delay_track_push(self.h, mic_ptr, ref_ptr, int(ld_in), out_ptr, int(ld_out), hops_ptr,
                                             int(max_hops), delay_ptr, curve_ptr, stream), self.h,
               'aec_delay_track_push')
+
+    def drift_track_open(self, B, seg_frames, pairs, gain, max_ppm, ngrid, latency, init_ppm):
+        cfg = DriftTrackConfig(int(seg_frames), int(pairs), int(ngrid), int(latency), float(gain), float(max_ppm),
+                               float(init_ppm))
+        check(self.lib.aec_drift_track_open(self.h, int(B), ctypes.byref(cfg)), self.h, 'aec_drift_track_open')
+
+    def drift_track_reset(self, b, stream):
+        check(self.lib.aec_drift_track_reset(self.h, int(b), stream), self.h, 'aec_drift_track_reset')
+
+    def drift_track_push(self, mic_ptr, ref_ptr, ld_in, out_ptr, ld_out, hops_ptr, max_hops, shift_ptr, ppm_ptr,
+                         curve_ptr, counters_ptr, stream):
+        """hops_ptr, shift_ptr: device [B] int32 or None; ppm_ptr: device [B] float32 or None; curve_ptr:
+        device [B, ngrid] or None; counters_ptr: device [B, 2] int32 or None"""
+        check(self.lib.aec_drift_track_push(self.h, mic_ptr, ref_ptr, int(ld_in), out_ptr, int(ld_out), hops_ptr,
+                                            int(max_hops), shift_ptr, ppm_ptr, curve_ptr, counters_ptr, stream),
+              self.h, 'aec_drift_track_push')
 
     def debug_copy(self, what, dst_ptr, n, stream):
         check(self.lib.aec_debug_copy(self.h, int(what), dst_ptr, int(n), stream), self.h, 'aec_debug_copy')

@@ -19,6 +19,7 @@
 #include "../../include/aec_hip.h"
 #include "aec_delay.h"
 #include "aec_drift.h"
+#include "aec_drift_track.h"
 #include "aec_device.h"
 #include "aec_host.h"
 #include "aec_launch.h"
@@ -125,6 +126,10 @@ struct aec_handle {
     int32_t track_B = 0;
     int64_t track_stride = 0;
     aec_delay_track_config track_cfg{};
+    // streaming drift tracker (aec_drift_track_*): per-stream state [dtrack_B][kDriftTrackStateFloats]
+    float* d_dtrack = nullptr;
+    int32_t dtrack_B = 0;
+    DriftTrackCfg dtrack_cfg{};
     // training (aec_train_*): state of the last aec_train_forward, read by aec_train_backward
     float* d_th = nullptr;       // [B][T][32] GRU outputs
     float* d_tloss = nullptr;    // [B] per-row loss
@@ -1128,7 +1133,7 @@ void aec_destroy(aec_handle* h) {
     (void)hipFree(h->d_mom); (void)hipFree(h->d_cvals); (void)hipFree(h->d_lists);
     (void)hipFree(h->d_feats); (void)hipFree(h->d_est); (void)hipFree(h->d_dbg); (void)hipFree(h->d_spec);
     (void)hipFree(h->d_state); (void)hipFree(h->d_rows); (void)hipFree(h->d_progress);
-    (void)hipFree(h->d_track); (void)hipFree(h->d_drift_tab);
+    (void)hipFree(h->d_track); (void)hipFree(h->d_drift_tab); (void)hipFree(h->d_dtrack);
     if (h->h_pipe_err) (void)hipHostFree(h->h_pipe_err);
     (void)hipFree(h->d_th); (void)hipFree(h->d_tloss); (void)hipFree(h->d_rec); (void)hipFree(h->d_dg);
     (void)hipFree(h->d_part); (void)hipFree(h->d_scan);
@@ -1184,6 +1189,64 @@ aec_status aec_delay_track_push(aec_handle* h, const float* mic, const float* re
     a.max_lag = h->track_cfg.max_lag; a.period = h->track_cfg.period; a.hold = h->track_cfg.hold;
     a.lead = h->track_cfg.lead; a.forget = h->track_cfg.forget; a.ratio = h->track_cfg.ratio;
     HIP_TRY(h, launch_delay_track(a, h->track_B, reinterpret_cast<hipStream_t>(stream)));
+    return AEC_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The far-end clock drift while streaming (kernel in aec_drift_track.hip, checks in aec_host.h).
+// As the delay tracker above, the state belongs to the tracker alone.  All zeros is the start
+// state (the kernel takes ppm, anchor and shift from the config on a stream's first hop), so reset
+// is a memset in stream order.
+// ---------------------------------------------------------------------------
+static_assert(sizeof(aec_drift_track_config) == sizeof(DriftTrackCfg), "one layout for the ABI and the kernel");
+
+aec_status aec_drift_track_open(aec_handle* h, int32_t B, const aec_drift_track_config* cfg) {
+    if (!h) return AEC_ERR_INVALID_ARG;
+    if (!cfg) return fail(h, AEC_ERR_INVALID_ARG, "null config");
+    DriftTrackCfg c{};
+    c.seg_frames = cfg->seg_frames; c.pairs = cfg->pairs; c.ngrid = cfg->ngrid; c.latency = cfg->latency;
+    c.gain = cfg->gain; c.max_ppm = cfg->max_ppm; c.init_ppm = cfg->init_ppm;
+    const Check ck = check_drift_track_open(B, c);
+    if (ck.status != AEC_OK) return fail(h, ck.status, ck.why);
+    AEC_ON_DEVICE(h);
+    HIP_TRY(h, hipDeviceSynchronize());   // a previous state may still be in use
+    if (h->d_dtrack) { HIP_TRY(h, hipFree(h->d_dtrack)); h->d_dtrack = nullptr; }
+    h->dtrack_B = 0;
+    const size_t bytes = (size_t)B * kDriftTrackStateFloats * sizeof(float);
+    HIP_TRY(h, hipMalloc(&h->d_dtrack, bytes));
+    HIP_TRY(h, hipMemset(h->d_dtrack, 0, bytes));
+    h->dtrack_B = B;
+    h->dtrack_cfg = c;
+    return AEC_OK;
+}
+
+aec_status aec_drift_track_reset(aec_handle* h, int32_t b, void* stream) {
+    if (!h) return AEC_ERR_INVALID_ARG;
+    if (!h->d_dtrack) return fail(h, AEC_ERR_INVALID_ARG, "aec_drift_track_open first");
+    if (b < -1 || b >= h->dtrack_B) return fail(h, AEC_ERR_INVALID_ARG, "stream index out of range");
+    AEC_ON_DEVICE(h);
+    const int64_t first = b < 0 ? 0 : b, count = b < 0 ? h->dtrack_B : 1;
+    HIP_TRY(h, hipMemsetAsync(h->d_dtrack + first * kDriftTrackStateFloats, 0,
+                              (size_t)count * kDriftTrackStateFloats * sizeof(float), reinterpret_cast<hipStream_t>(stream)));
+    return AEC_OK;
+}
+
+aec_status aec_drift_track_push(aec_handle* h, const float* mic, const float* ref, int64_t ld_in, float* ref_out,
+                                int64_t ld_out, const int32_t* hops, int32_t max_hops, const int32_t* shift,
+                                float* drift_ppm, float* curve, int32_t* counters, void* stream) {
+    if (!h) return AEC_ERR_INVALID_ARG;
+    const Check c = check_drift_track_args(h->d_dtrack != nullptr, mic, ref, ref_out, max_hops, ld_in, ld_out);
+    if (c.status != AEC_OK) return fail(h, c.status, c.why);
+    AEC_ON_DEVICE(h);
+    DriftTrackArgs a{};
+    a.mic = mic; a.ref = ref; a.ld_in = ld_in; a.ref_out = ref_out; a.ld_out = ld_out;
+    a.hops = hops; a.max_hops = max_hops; a.shift = shift;
+    a.drift_ppm = drift_ppm; a.curve = curve; a.counters = counters;
+    a.state = h->d_dtrack;
+    a.tables = reinterpret_cast<const float*>(h->d_tab);
+    a.table = h->d_drift_tab;
+    a.cfg = h->dtrack_cfg;
+    HIP_TRY(h, launch_drift_track(a, h->dtrack_B, reinterpret_cast<hipStream_t>(stream)));
     return AEC_OK;
 }
 

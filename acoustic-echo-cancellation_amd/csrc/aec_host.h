@@ -15,6 +15,7 @@
 #include "../../include/aec_hip.h"
 #include "aec_canceller.h"
 #include "aec_drift.h"
+#include "aec_drift_track.h"
 
 namespace aec {
 
@@ -370,6 +371,28 @@ inline Check check_delay_track(bool open, const void* mic, const void* ref, cons
     if (c.status != AEC_OK) return c;
     if ((int64_t)256 * max_hops > kDelayMaxLen) return {AEC_ERR_UNSUPPORTED, "packet longer than 2^29 - 4096 samples"};
     if (ref_out == ref) return {AEC_ERR_INVALID_ARG, "ref_out must not be ref (the alignment cannot run in place)"};
+    return {};
+}
+
+// The streaming drift tracker (aec_drift_track_*; kernel, state layout and the parameter ranges in
+// aec_drift_track.h).  Open: B and aec_drift_track_config field by field.
+inline Check check_drift_track_open(int32_t B, const DriftTrackCfg& cfg) {
+    if (B < 1) return {AEC_ERR_INVALID_ARG, "B must be >= 1"};
+    if (const char* why = drift_track_cfg_error(cfg)) return {AEC_ERR_INVALID_ARG, why};
+    return {};
+}
+
+// aec_drift_track_push's packet: aec_delay_track_push's rules (`open` says whether the handle has a
+// drift tracker; every row holds max_hops hops; the resampled hops cannot be written over the
+// reference they are formed from; 32-bit byte offsets into a row)
+inline Check check_drift_track_args(bool open, const void* mic, const void* ref, const void* ref_out, int32_t max_hops,
+                                    int64_t ld_in, int64_t ld_out) {
+    if (!open) return {AEC_ERR_INVALID_ARG, "aec_drift_track_open first"};
+    if (!mic || !ref || !ref_out) return {AEC_ERR_INVALID_ARG, "null mic / ref / ref_out"};
+    const Check c = check_stream_push(max_hops, ld_in, ld_out);
+    if (c.status != AEC_OK) return c;
+    if ((int64_t)256 * max_hops > kDelayMaxLen) return {AEC_ERR_UNSUPPORTED, "packet longer than 2^29 - 4096 samples"};
+    if (ref_out == ref) return {AEC_ERR_INVALID_ARG, "ref_out must not be ref (the resampler cannot run in place)"};
     return {};
 }
 

@@ -357,6 +357,76 @@ aec_status aec_delay_track_push(aec_handle* h, const float* mic, const float* re
                                 int64_t ld_out, const int32_t* hops, int32_t max_hops, int32_t* delay, float* curve,
                                 void* stream);
 
+/* The far-end clock drift while streaming (no reference counterpart; DESIGN.md
+ * 27): aec_drift_estimate / aec_drift_apply as a closed loop over live streams,
+ * with aec_delay_track_push's contract.  The resampler sits in front of the
+ * delay tracker, so that one sees a constant lag:
+ *   aec_drift_track_push(h, mic, ref, ld, res, ld, hops, K, delay, ppm, NULL, NULL, st);
+ *   aec_delay_track_push(h, mic, res, ld, aligned, ld, hops, K, delay, NULL, st);
+ *   aec_stream_push(h, mic, aligned, ld, out, ld, hops, K, st);
+ * The estimator reads the residual drift between the mic and its own resampled
+ * output, read `shift` frames late (the delay tracker's latest delay, device data).
+ * Sign, table h[257][32], taps j = -15..16, the ph / a blend, the +-2000 ppm clamp
+ * and NaN -> 0 are aec_drift_apply's; frames, bins, the PHAT step, J, its first
+ * maximiser and the parabola are aec_drift_estimate's.
+ * Start / reset: ppm = clamp(init_ppm), anchor A = -latency (double), iA = 0,
+ * t = 0, C = Cp = D = 0, have_prev = npairs = fs = 0, cur_shift = -1, updates =
+ * slips = 0, rings zero.
+ * Per call, before its first hop: s = shift[b] clamped to [0, 63] (0 when shift is
+ * NULL); if s != cur_shift the cycle restarts: C = D = 0, fs = npairs = have_prev
+ * = 0, cur_shift = s.  Per stream and hop h = t, in this order:
+ *   1. q = 1 / (1 + (double)ppm 1e-6), every operation rounded on its own.  If q
+ *      differs from the previous hop's q_old: A += (double)(256 h - iA) q_old,
+ *      iA = 256 h.  The read position stays continuous across a rate change.
+ *   2. first = A + (double)(256 h - iA) q, last = A + (double)(256 h + 255 - iA) q.
+ *      If floor(last) + 16 > 256 h + 255 (the reads would pass the newest sample)
+ *      or floor(first) - 15 < 256 (h + 1) - 16384 (they would leave the 64-hop
+ *      input ring): A = 256 h - latency, iA = 256 h, slips += 1.
+ *   3. for i = 256 h .. 256 h + 255: p = A + (double)(i - iA) q, i0 = floor(p),
+ *      fr = (float)(p - i0), then aec_drift_apply's blend and 32-tap sum in tap
+ *      order; ref reads as 0 at negative indices.  The result is ref_out's hop
+ *      and enters a ring of the last 65 output hops.
+ *   4. M = bins 1..255 of mic frame h, O = the same of the OUTPUT frame h - s
+ *      (zero when h - s < 0); C[k] += M[k] conj(O[k]), fs += 1.
+ *   5. when fs == S: fs = 0; if have_prev: Z = C conj(Cp), D += Z / sqrt(|Z|^2 +
+ *      1e-30), npairs += 1; then Cp = C, C = 0, have_prev = 1.  If npairs ==
+ *      pairs: J[g] from D as aec_drift_estimate forms it, r = its first maximiser
+ *      plus the parabola (float32), ppm = clamp(ppm + gain r) (product and sum
+ *      each rounded to float32), updates += 1, D = 0, npairs = have_prev = 0.  The
+ *      new rate acts from hop h + 1.  No pair spans a rate change.
+ * With gain 0, latency 256 m and a stream shorter than the ring, ref_out is
+ * aec_drift_apply's output at shift m, bit for bit.
+ *   aec_drift_track_open(h, B, cfg)   B trackers: seg_frames S 4..64, pairs 1..16,
+ *        gain [0, 1] (0: a fixed-rate streaming resampler), max_ppm (0, 2000],
+ *        ngrid odd 3..255, latency 16..8192 samples, init_ppm clamped like any ppm.
+ *        Independent of every other state of the handle.  Opening again replaces
+ *        the state; aec_destroy frees it (35088 floats = 137.06 KiB per stream).
+ *   aec_drift_track_reset(h, b, st)   stream b (-1: every stream) back to the start
+ *   aec_drift_track_push(...)
+ *        mic, ref, ld_in, ref_out, ld_out, hops, max_hops: exactly as in
+ *             aec_delay_track_push
+ *        shift:     DEVICE [B] int32 frames, or NULL
+ *        drift_ppm: device [B] float32 receives the rate after the packet, or NULL
+ *        curve:     device [B, ngrid] receives the latest J (zeros before the
+ *             first update), or NULL
+ *        counters:  device [B, 2] int32 receives updates, slips, or NULL
+ *        A stream with 0 hops changes no byte of its state or of its rows in any
+ *        output.  Asynchronous: never synchronises.
+ * A stream's results depend on its own samples, its shifts and the open
+ * parameters alone: not on B, its row or the strides, and for a constant shift
+ * not on how its hops are cut into packets (bit for bit).  AEC_ERR_INVALID_ARG
+ * (text in aec_last_error): as aec_delay_track_*, and each parameter outside its
+ * range. */
+typedef struct {
+    int32_t seg_frames, pairs, ngrid, latency;
+    float gain, max_ppm, init_ppm;
+} aec_drift_track_config;
+aec_status aec_drift_track_open(aec_handle* h, int32_t B, const aec_drift_track_config* cfg);
+aec_status aec_drift_track_reset(aec_handle* h, int32_t b, void* stream);
+aec_status aec_drift_track_push(aec_handle* h, const float* mic, const float* ref, int64_t ld_in, float* ref_out,
+                                int64_t ld_out, const int32_t* hops, int32_t max_hops, const int32_t* shift,
+                                float* drift_ppm, float* curve, int32_t* counters, void* stream);
+
 /* Debug / parity: copy an intermediate of the LAST aec_process call into the
  * device buffer dst ([B, T_max, 32] float32, frames beyond a stream's T left
  * unspecified).  Requires aec_set_debug(h, 1) before that call.
