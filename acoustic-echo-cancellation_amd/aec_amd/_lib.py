@@ -23,7 +23,8 @@ AEC_ERR_UNSUPPORTED = 4
 _STATUS = {0: 'AEC_OK', 1: 'AEC_ERR_INVALID_ARG', 2: 'AEC_ERR_OOM', 3: 'AEC_ERR_HIP', 4: 'AEC_ERR_UNSUPPORTED'}
 
 # every symbol include/aec_hip.h declares
-EXPORTS = ('aec_weights_count', 'aec_create', 'aec_set_weights', 'aec_set_erb', 'aec_set_canceller', 'aec_process',
+EXPORTS = ('aec_weights_count', 'aec_create', 'aec_set_weights', 'aec_set_erb', 'aec_set_canceller', 'aec_set_canceller_rescue',
+           'aec_process',
            'aec_process_siglens',
            'aec_prepare', 'aec_prepare_siglens', 'aec_process_prepared',
            'aec_stream_open', 'aec_stream_reset', 'aec_stream_step', 'aec_stream_push',
@@ -100,6 +101,9 @@ def load():
     if LIB_PATH == _DEFAULT_LIB or hasattr(lib, 'aec_set_canceller'):
         lib.aec_set_canceller.argtypes = [P, ctypes.c_int32, ctypes.c_float, ctypes.c_float]
         lib.aec_set_canceller.restype = ctypes.c_int
+    if LIB_PATH == _DEFAULT_LIB or hasattr(lib, 'aec_set_canceller_rescue'):   # absent from an older A/B build
+        lib.aec_set_canceller_rescue.argtypes = [P, ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float]
+        lib.aec_set_canceller_rescue.restype = ctypes.c_int
     lib.aec_process.argtypes = [P, P, P, P, P, ctypes.c_int32, ctypes.c_int64, P, ctypes.c_int64, P, P]
     lib.aec_process.restype = ctypes.c_int
     lib.aec_process_siglens.argtypes = [P, P, P, P, P, ctypes.c_int32, ctypes.c_int64, P, ctypes.c_int64, P, P]
@@ -289,6 +293,11 @@ class Handle:
         """kind: 'nlms' / 0 or 'kalman' / 1 (aec_set_canceller)."""
         kind = {'nlms': 0, 'kalman': 1}.get(kind, kind)
         check(self.lib.aec_set_canceller(self.h, int(kind), float(a), float(p0)), self.h, 'aec_set_canceller')
+
+    def set_canceller_rescue(self, on, mu=0.3, gamma=0.9, ratio=0.5):
+        """The Kalman canceller's rescue from echo-path changes (aec_set_canceller_rescue)."""
+        check(self.lib.aec_set_canceller_rescue(self.h, int(bool(on)), float(mu), float(gamma), float(ratio)), self.h,
+              'aec_set_canceller_rescue')
 
     def set_debug(self, on: bool):
         check(self.lib.aec_set_debug(self.h, int(bool(on))), self.h, 'aec_set_debug')

@@ -68,3 +68,9 @@ kalman_conf = {
     'delta': 1e-4,
     'p0': 1.0,
 }
+
+# kalman_conf with the rescue from abrupt echo-path changes (include/aec_hip.h
+# aec_set_canceller_rescue): a shadow FD-NLMS with step mu, error
+# powers smoothed with gamma, the shadow copied in when its error power falls
+# below ratio times the Kalman filter's.  1..8 taps, the batch path.
+kalman_rescue_conf = dict(kalman_conf, rescue=True, mu=0.3, gamma=0.9, ratio=0.5)

@@ -185,6 +185,10 @@ class Little_net(nn.Module):
                 h.set_canceller('kalman', nl.get('a', 0.999), nl.get('p0', 1.0))
             elif kind != 'nlms':
                 raise ValueError(f"nlms['kind'] must be 'nlms' or 'kalman', got {kind!r}")
+            if nl.get('rescue'):
+                if kind != 'kalman':
+                    raise ValueError("nlms['rescue'] belongs to the Kalman canceller (kind='kalman')")
+                h.set_canceller_rescue(True, nl.get('mu', 0.3), nl.get('gamma', 0.9), nl.get('ratio', 0.5))
             self._handles[idx] = h
         if not upload:
             return h, idx
@@ -419,10 +423,11 @@ class Little_net(nn.Module):
 
     def debug_intermediate(self, what, B, T, device=None):
         """Copy an intermediate of the last forward: 'mic_erb', 'ref_erb',
-        'near_erb', 'gru_out', 'mask', 'est_erb' -> [B, T, 32]."""
-        codes = dict(mic_erb=0, ref_erb=1, near_erb=2, gru_out=3, mask=4, est_erb=5)
+        'near_erb', 'gru_out', 'mask', 'est_erb' -> [B, T, 32]; 'rescue_mask' (the
+        canceller rescue's copy decisions, 1 = the shadow was copied) -> [B, T, 257]."""
+        codes = dict(mic_erb=0, ref_erb=1, near_erb=2, gru_out=3, mask=4, est_erb=5, rescue_mask=6)
         device = torch.device(device or 'cuda')
         h, _ = self._handle(device)
-        dst = torch.empty(B, T, 32, device=device, dtype=torch.float32)
+        dst = torch.empty(B, T, 257 if what == 'rescue_mask' else 32, device=device, dtype=torch.float32)
         h.debug_copy(codes[what], dst.data_ptr(), dst.numel(), torch.cuda.current_stream(device).cuda_stream)
         return dst

@@ -72,6 +72,37 @@ def scene(n, seed, double_talk=True, return_echo=False, rir_taps=1024, t60=0.25)
     return out
 
 
+def scene_path_change(n, seed, double_talk=True, change_at=None, return_echo=False):
+    """scene() with an abrupt echo-path change: a second room response takes over at
+    sample change_at (default n // 2).  Draws, in order: ref, h1 = rir, h2 = rir, then
+    near and noise as scene does; echo = ref * h1 before change_at and ref * h2 from it
+    on, both scaled by the factor that puts ref * h1 at -6 dB relative to ref."""
+    from scipy.signal import fftconvolve
+    rng = np.random.default_rng(seed)
+    if change_at is None:
+        change_at = n // 2
+    ref = _ar1(rng, n) * _envelope(rng, n)
+    ref *= 0.1 / _rms(ref)
+    h1 = rir(rng)
+    h2 = rir(rng)
+    e1 = fftconvolve(ref, h1)[:n]
+    e2 = fftconvolve(ref, h2)[:n]
+    echo = np.where(np.arange(n) < change_at, e1, e2) * ((_rms(ref) * 10 ** (-6 / 20)) / _rms(e1))
+    if double_talk:
+        near = _ar1(rng, n, a=0.7) * _envelope(rng, n, rate_hz=2.5)
+        gate = (np.sin(2 * np.pi * 0.4 * np.arange(n) / SR + rng.uniform(0, 6.28)) > 0.2)
+        near *= gate
+        near *= (_rms(ref) * 10 ** (-3 / 20)) / max(_rms(near), 1e-12)
+    else:
+        near = np.zeros(n)
+    noise = rng.standard_normal(n) * _rms(ref) * 10 ** (-50 / 20)
+    mic = echo + near + noise
+    out = (mic.astype(np.float32), ref.astype(np.float32), near.astype(np.float32))
+    if return_echo:
+        out = out + (echo.astype(np.float32),)
+    return out
+
+
 def batch(B, n, seed0=0, double_talk=True):
     """[B, n] float32 arrays (mic, ref, near) with per-stream seeds seed0+b."""
     mic = np.empty((B, n), np.float32)

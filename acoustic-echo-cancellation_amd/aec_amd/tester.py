@@ -29,6 +29,8 @@ Extra flags (all optional):
 - `--nlms` puts the FD-NLMS stage in front of the post-filter;
 - `--kalman` puts the frequency-domain Kalman canceller there instead
   (`configs.kalman_conf`; the two flags exclude each other);
+- `--rescue` with `--kalman` switches on the Kalman canceller's rescue from
+  abrupt echo-path changes (`configs.kalman_rescue_conf`; 1..8 taps);
 - `--taps N` sets the canceller's taps per bin (1..16 frames of far-end
   history, 16 ms each; default: the configuration's 4) for `--nlms` / `--kalman`;
 - `--align MAX_LAG` estimates each utterance's far-end bulk delay over lags of
@@ -55,7 +57,7 @@ from typing import Callable, List, Optional, Sequence
 import numpy as np
 
 from . import h5lite, shard, wavio
-from .configs import erb_conf, kalman_conf, nlms_conf, speech_conf
+from .configs import erb_conf, kalman_conf, kalman_rescue_conf, nlms_conf, speech_conf
 
 # enhance(mic, ref, near, lengths[B][3] = (mic, ref, near) lengths) -> list of
 # 1-D float32 outputs, one per row, each 256*(n_mic//256) samples
@@ -88,6 +90,8 @@ def build_parser():
     lin.add_argument('--nlms', action='store_true', help='FD-NLMS linear AEC in front of the post-filter')
     lin.add_argument('--kalman', action='store_true',
                      help='frequency-domain Kalman linear AEC in front of the post-filter')
+    p.add_argument('--rescue', action='store_true',
+                   help='with --kalman: recover from abrupt echo-path changes through a shadow FD-NLMS (1..8 taps)')
     p.add_argument('--taps', type=int, default=None, choices=range(1, 17), metavar='N',
                    help='taps per bin of the --nlms / --kalman canceller, 1..16 (default: the configuration\'s 4)')
     p.add_argument('--align', type=int, default=None, metavar='MAX_LAG',
@@ -137,6 +141,10 @@ class Tester(object):
         local = self.args.device if self.args.device is not None else shard.local_rank()
         device = torch.device('cuda', local)
         lin = kalman_conf if getattr(self.args, 'kalman', False) else (nlms_conf if self.args.nlms else None)
+        if getattr(self.args, 'rescue', False):
+            if lin is not kalman_conf:
+                raise SystemExit('--rescue needs --kalman')
+            lin = kalman_rescue_conf
         if lin is not None and getattr(self.args, 'taps', None) is not None:
             lin = dict(lin, taps=self.args.taps)
         net = Little_net(speech_conf, erb_conf['total_erb_bands'], nlms=lin)

@@ -88,6 +88,10 @@ struct aec_handle {
     // the linear stage's adaptive filter (aec_set_canceller): 0 FD-NLMS, 1 frequency-domain Kalman
     CancellerChoice canc;
     Canceller canceller() const { return make_canceller(cfg, canc); }
+    // the Kalman canceller's rescue (aec_set_canceller_rescue), and in debug mode its copy decisions
+    CancellerRescue rescue;
+    float* d_rmask = nullptr;    // [B][T][257]
+    size_t rmask_cap = 0;        // floats
     std::vector<int64_t> last_lens;                 // [B][3] of the last call (work lists rebuilt on change)
     int debug = 0;
     int gru_mode = 0;            // AEC_GRU_MODE (A/B builds: timing experiments; results invalid unless 0)
@@ -230,6 +234,7 @@ const char* aec_last_error(const aec_handle* h) { return h ? h->err.c_str() : "n
 
 const char* aec_build_info(void) {
     static const std::string info = std::string("arch=gfx950 ab_knobs=") + (AEC_AB_BUILD ? "on" : "off") +
+                                    " canceller_rescue=kalman:1-" + std::to_string(aec::kRescueMaxTaps) +
                                     " mode_knobs=" + aec::kModeKnobs;
     return info.c_str();
 }
@@ -256,6 +261,18 @@ aec_status aec_set_canceller(aec_handle* h, int32_t kind, float a, float p0) {
         h->canc.p0 = p0;
     }
     h->canc.kind = kind;
+    h->rescue.on = 0;
+    return AEC_OK;
+}
+
+aec_status aec_set_canceller_rescue(aec_handle* h, int32_t on, float mu, float gamma, float ratio) {
+    if (!h) return AEC_ERR_INVALID_ARG;
+    bool unsupported = false;
+    const std::string why = check_canceller_rescue(h->cfg.nlms_taps, h->canc.kind, on, mu, gamma, ratio,
+                                                   h->d_state != nullptr, &unsupported);
+    if (!why.empty()) return fail(h, unsupported ? AEC_ERR_UNSUPPORTED : AEC_ERR_INVALID_ARG, why);
+    if (on) h->rescue = CancellerRescue{1, mu, gamma, ratio};
+    else h->rescue.on = 0;
     return AEC_OK;
 }
 
@@ -518,7 +535,7 @@ static aec_status process_impl(aec_handle* h, uint64_t token, const float* mic, 
     AEC_ON_DEVICE(h);
     // which kernels run (aec_host.h); AEC_GRU_NS is a mode knob read per call
     const Plan p = plan_call({h->cfg.nlms_taps, B, h->small_b, h->nlms_mode, h->small_pipe, h->fused, h->gru_mode,
-                              h->num_cus, AEC_MODE_KNOB("AEC_GRU_NS", 0), token != 0, h->canc.kind});
+                              h->num_cus, AEC_MODE_KNOB("AEC_GRU_NS", 0), token != 0, h->canc.kind, h->rescue.on});
     if (p.nlms_batch && nlms_smem_bytes(h->sched_len, h->cfg.nlms_taps) > 160 * 1024)   // before any launch
         return fail(h, AEC_ERR_UNSUPPORTED, "erb schedule too long for the NLMS kernel's LDS budget");
     // aec_process_prepared: the look-ahead pass named by `token` (aec_prepare_siglens), checked
@@ -575,6 +592,12 @@ static aec_status process_impl(aec_handle* h, uint64_t token, const float* mic, 
             if (s != AEC_OK) return s;
         }
     }
+    const bool rmask = p.split && h->rescue.on && h->debug;      // the rescue's copy decisions, for aec_debug_copy
+    if (rmask && (size_t)B * Tmax * 257 > h->rmask_cap) {
+        const size_t need = (size_t)B * Tmax * 257;
+        s = grow_after_last(h, h->d_rmask, h->rmask_cap, need, need * sizeof(float), true);
+        if (s != AEC_OK) return s;
+    }
     // the last return with nothing launched is behind: the look-ahead is consumed, and the pending
     // passes queued before it are dropped (their slots stay fenced by their done / freed events)
     if (ps) h->ring.consume(pre_k);
@@ -608,8 +631,11 @@ static aec_status process_impl(aec_handle* h, uint64_t token, const float* mic, 
         mark(h, st);
         HIP_TRY(h, launch_analysis(a, st));
         if (p.split && !p.pipe) {      // few streams: recursion per stream, then mic_erb frame-parallel
-            HIP_TRY(h, launch_recursion({h->d_rows, h->d_spec, h->d_len, Tmax, 0, B, h->d_rows + (size_t)B * Tmax * 512},
-                                        h->canceller(), st));
+            const RecursionArgs ra{h->d_rows, h->d_spec, h->d_len, Tmax, 0, B, h->d_rows + (size_t)B * Tmax * 512};
+            if (h->rescue.on)
+                HIP_TRY(h, launch_recursion_rescue(ra, h->canceller(), h->rescue, rmask ? h->d_rmask : nullptr, st));
+            else
+                HIP_TRY(h, launch_recursion(ra, h->canceller(), st));
             HIP_TRY(h, launch_mic_erb(h->d_spec, h->d_feats, h->d_len, Tmax, h->d_sched, h->sched_len, h->d_items,
                                       a.nitems, st));
         }
@@ -714,10 +740,12 @@ aec_status aec_prepare(aec_handle* h, const float* mic, const float* ref, const 
 aec_status aec_debug_copy(aec_handle* h, int32_t what, float* dst, size_t n, void* stream) {
     if (!h) return AEC_ERR_INVALID_ARG;
     const int64_t B = h->last_B, T = h->last_T;
-    if (!dst || n < (size_t)(B * T * 32)) return fail(h, AEC_ERR_INVALID_ARG, "dst too small");
+    if (!dst || n < (size_t)(B * T * (what == 6 ? 257 : 32))) return fail(h, AEC_ERR_INVALID_ARG, "dst too small");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     AEC_ON_DEVICE(h);
-    if (what < 0 || what > 5) return fail(h, AEC_ERR_INVALID_ARG, "unknown intermediate");
+    if (what < 0 || what > 6) return fail(h, AEC_ERR_INVALID_ARG, "unknown intermediate");
+    if (what == 6 && (!h->debug || !h->rescue.on || (size_t)(B * T * 257) > h->rmask_cap || B * T == 0))
+        return fail(h, AEC_ERR_INVALID_ARG, "rescue_mask: aec_set_canceller_rescue and aec_set_debug before aec_process");
     if ((what == 3 || what == 4) && !h->debug) return fail(h, AEC_ERR_INVALID_ARG, "enable aec_set_debug before aec_process");
     // ordered after the last call (it may have run on another stream) like any other call
     aec_status s = begin_call(h, st);
@@ -726,6 +754,8 @@ aec_status aec_debug_copy(aec_handle* h, int32_t what, float* dst, size_t n, voi
     if (what >= 0 && what <= 2) {
         HIP_TRY(h, hipMemcpy2DAsync(dst, 32 * sizeof(float), h->d_feats + 32 * what, 96 * sizeof(float),
                                     32 * sizeof(float), B * T, hipMemcpyDeviceToDevice, st));
+    } else if (what == 6) {
+        HIP_TRY(h, hipMemcpyAsync(dst, h->d_rmask, B * T * 257 * sizeof(float), hipMemcpyDeviceToDevice, st));
     } else if (what == 3 || what == 4) {
         if (!h->debug) return fail(h, AEC_ERR_INVALID_ARG, "enable aec_set_debug before aec_process");
         HIP_TRY(h, hipMemcpyAsync(dst, h->d_dbg + (what - 3) * B * T * 32, B * T * 32 * sizeof(float),
@@ -777,6 +807,7 @@ aec_status aec_erb_tables_check(const float* erb, const float* mags, const float
 aec_status aec_stream_open(aec_handle* h, int32_t B) {
     if (!h) return AEC_ERR_INVALID_ARG;
     if (B < 1) return fail(h, AEC_ERR_INVALID_ARG, "stream count must be >= 1");
+    if (h->rescue.on) return fail(h, AEC_ERR_UNSUPPORTED, "the streaming kernels have no canceller rescue (aec_set_canceller_rescue)");
     AEC_ON_DEVICE(h);
     HIP_TRY(h, hipDeviceSynchronize());   // a previous state may still be in use
     if (h->d_state) { HIP_TRY(h, hipFree(h->d_state)); h->d_state = nullptr; }
@@ -1132,7 +1163,7 @@ void aec_destroy(aec_handle* h) {
     }
     (void)hipFree(h->d_mom); (void)hipFree(h->d_cvals); (void)hipFree(h->d_lists);
     (void)hipFree(h->d_feats); (void)hipFree(h->d_est); (void)hipFree(h->d_dbg); (void)hipFree(h->d_spec);
-    (void)hipFree(h->d_state); (void)hipFree(h->d_rows); (void)hipFree(h->d_progress);
+    (void)hipFree(h->d_state); (void)hipFree(h->d_rows); (void)hipFree(h->d_progress); (void)hipFree(h->d_rmask);
     (void)hipFree(h->d_track); (void)hipFree(h->d_drift_tab); (void)hipFree(h->d_dtrack);
     if (h->h_pipe_err) (void)hipHostFree(h->h_pipe_err);
     (void)hipFree(h->d_th); (void)hipFree(h->d_tloss); (void)hipFree(h->d_rec); (void)hipFree(h->d_dg);

@@ -62,6 +62,36 @@ inline std::string check_canceller(int taps, int kind, float a, float p0, bool s
     return "";
 }
 
+// The Kalman canceller's two-path rescue (aec_set_canceller_rescue): a shadow
+// FD-NLMS with step mu beside the main filter, the two error powers smoothed with gamma, and the
+// shadow's taps copied into the main filter (covariances back to p0) when the shadow's error
+// power falls below ratio times the main filter's.  Off on every handle that does not ask for it.
+constexpr int kRescueMaxTaps = 8;      // the rescue recursion (aec_rescue.hip) is instantiated for 1..8 taps
+struct CancellerRescue {
+    int32_t on = 0;
+    float mu = 0.3f, gamma = 0.9f, ratio = 0.5f;
+};
+static_assert(std::is_trivially_copyable<CancellerRescue>::value, "CancellerRescue travels in kernel argument blocks");
+
+// aec_set_canceller_rescue's argument rules, as check_canceller states aec_set_canceller's.  kind:
+// the handle's selected canceller.  The values are checked only when the call switches the rescue on.
+inline std::string check_canceller_rescue(int taps, int kind, int on, float mu, float gamma, float ratio,
+                                          bool stream_open, bool* unsupported) {
+    *unsupported = false;
+    if (kind != kCancellerKalman) return "the rescue belongs to the Kalman canceller: select it with aec_set_canceller first";
+    if (taps < 1 || taps > kRescueMaxTaps) {
+        *unsupported = true;
+        return "the canceller rescue exists for 1..8 taps";
+    }
+    if (stream_open) return "a streaming state is open: the streaming kernels have no rescue";
+    if (on) {
+        if (!(mu >= 0.f && std::isfinite(mu))) return "rescue step size mu must be finite and >= 0";
+        if (!(gamma >= 0.f && gamma < 1.f)) return "rescue smoothing factor gamma must be in [0, 1)";
+        if (!(ratio >= 0.f && std::isfinite(ratio))) return "rescue ratio must be finite and >= 0";
+    }
+    return "";
+}
+
 // --------------------------------------------------------------------------
 // state layout
 // --------------------------------------------------------------------------

@@ -171,6 +171,11 @@ struct RecursionArgs {
 // KalmanBin::step.  launch_recursion forwards to launch_recursion_long above kK2nMaxTaps.
 hipError_t launch_recursion(const RecursionArgs& a, const Canceller& c, hipStream_t st);
 hipError_t launch_recursion_long(const RecursionArgs& a, const Canceller& c, hipStream_t st);
+// The Kalman canceller with its rescue on, 1..8 taps (aec_rescue.hip): the same rows in and E rows
+// out.  mask: null, or [B][Tmax][257] floats that receive the copy decisions (1 / 0 per bin and
+// frame; frames past a stream's end are left as they are), the debug instantiation.
+hipError_t launch_recursion_rescue(const RecursionArgs& a, const Canceller& c, const CancellerRescue& r, float* mask,
+                                   hipStream_t st);
 hipError_t launch_mic_erb(const float2* spec, float* feats, const int64_t* lens, int64_t Tmax, const float* sched,
                           int sched_len, const WorkItem* items, int64_t nitems, hipStream_t st);
 hipError_t launch_gru(const GruArgs& a, int B, hipStream_t st);

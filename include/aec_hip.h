@@ -101,6 +101,26 @@ aec_status aec_create(const aec_config* cfg, const float* weights, size_t n_weig
  * (aec_train_forward) stays the reference network's. */
 aec_status aec_set_canceller(aec_handle* h, int32_t kind, float a, float p0);
 
+/* The Kalman canceller's rescue from abrupt echo-path changes, off
+ * unless switched on here.  A converged Kalman filter has small covariances and
+ * re-adapts over seconds; with the rescue on, every bin also runs a shadow FD-NLMS
+ * (Ws, Pn) with step mu on the same far-end history and two smoothed error powers,
+ * all zero at each stream start.  Per frame, after the Kalman step above:
+ *   Es = D - sum_l Ws[l] R[t-l],  Pn = beta Pn + (1-beta) sum_l |R[t-l]|^2,
+ *   Ws[l] += mu Es conj(R[t-l]) / (Pn + delta),
+ *   qe = gamma qe + (1-gamma) |E|^2,  qs = gamma qs + (1-gamma) |Es|^2,
+ *   if qs < ratio qe:  W[l] = Ws[l], P[l] = p0 for every l;  qe = qs
+ * The output stays the Kalman filter's E.  ratio = 0 never copies (the plain
+ * Kalman canceller, bit for bit).  A rescue handle runs aec_process and
+ * aec_process_prepared through the K2 / per-stream recursion / mic_erb kernels at
+ * every batch size.  on = 0 switches it off (mu, gamma, ratio are then ignored),
+ * as does every later successful aec_set_canceller.
+ * AEC_ERR_INVALID_ARG: the Kalman canceller is not selected, a streaming state is
+ * open, or (on != 0) mu negative or not finite, gamma outside [0, 1), ratio
+ * negative or not finite.  AEC_ERR_UNSUPPORTED: nlms_taps > 8.  aec_stream_open on
+ * a handle with the rescue on returns AEC_ERR_UNSUPPORTED. */
+aec_status aec_set_canceller_rescue(aec_handle* h, int32_t on, float mu, float gamma, float ratio);
+
 aec_status aec_set_weights(aec_handle* h, const float* weights, size_t n_weights);
 aec_status aec_set_erb(aec_handle* h, const float* erb_257xbands);
 
@@ -431,7 +451,9 @@ aec_status aec_drift_track_push(aec_handle* h, const float* mic, const float* re
  * device buffer dst ([B, T_max, 32] float32, frames beyond a stream's T left
  * unspecified).  Requires aec_set_debug(h, 1) before that call.
  * what: 0 = mic_erb, 1 = ref_erb, 2 = near_erb, 3 = gru_out (h_t),
- *       4 = mask, 5 = est_erb. */
+ *       4 = mask, 5 = est_erb;
+ *       6 = rescue_mask: the canceller rescue's copy decisions of that call
+ *       (aec_set_canceller_rescue), dst [B, T_max, 257] float32, 1 = copied. */
 aec_status aec_set_debug(aec_handle* h, int32_t enable);
 aec_status aec_debug_copy(aec_handle* h, int32_t what, float* dst, size_t n_floats, void* stream);
 
