@@ -205,6 +205,50 @@ static aec_status grow_after_last(aec_handle* h, T*& p, C& cap, C new_cap, size_
     return AEC_OK;
 }
 
+// Per-stream state of the streaming calls (aec_stream_*, the delay tracker, the drift tracker): B
+// rows of `stride` floats, all zeros after open and after reset.  Open (on the handle's device)
+// waits for the device, since a previous state may still be in use, and replaces it; nB is 0 while
+// there is none.  Reset clears stream b, or all for b = -1, in stream order; `open_first` is the
+// text for a handle without the state.
+static aec_status state_open(aec_handle* h, float*& p, int32_t& nB, int32_t B, int64_t stride) {
+    HIP_TRY(h, hipDeviceSynchronize());
+    if (p) { HIP_TRY(h, hipFree(p)); p = nullptr; }
+    nB = 0;
+    HIP_TRY(h, hipMalloc(&p, (size_t)B * stride * sizeof(float)));
+    HIP_TRY(h, hipMemset(p, 0, (size_t)B * stride * sizeof(float)));
+    nB = B;
+    return AEC_OK;
+}
+static aec_status state_reset(aec_handle* h, float* p, int32_t nB, int64_t stride, int32_t b, const char* open_first,
+                              void* stream) {
+    if (!p) return fail(h, AEC_ERR_INVALID_ARG, open_first);
+    if (b < -1 || b >= nB) return fail(h, AEC_ERR_INVALID_ARG, "stream index out of range");
+    AEC_ON_DEVICE(h);
+    const int64_t first = b < 0 ? 0 : b, count = b < 0 ? nB : 1;
+    HIP_TRY(h, hipMemsetAsync(p + first * stride, 0, (size_t)count * stride * sizeof(float), reinterpret_cast<hipStream_t>(stream)));
+    return AEC_OK;
+}
+
+// The stateless far-end calls (delay and drift, estimate and apply): the host lengths ride in the
+// kernel arguments, kFrontRows streams per launch.  Fills a.b0 and a.len[] for each launch of a
+// batch and hands `launch` its rows and the longest of them; the first error ends it (the caller
+// wraps the call in HIP_TRY, so the message names its launcher).
+template <class Args, class Launch>
+static hipError_t launch_row_batches(Args& a, const int64_t* lengths, int32_t B, Launch&& launch) {
+    for (int32_t b0 = 0; b0 < B; b0 += kFrontRows) {
+        const int nb = std::min<int32_t>(kFrontRows, B - b0);
+        a.b0 = b0;
+        int64_t nmax = 0;
+        for (int i = 0; i < nb; ++i) {
+            a.len[i] = (int32_t)lengths[b0 + i];
+            nmax = std::max(nmax, lengths[b0 + i]);
+        }
+        const hipError_t e = launch(a, nb, nmax);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 namespace aec {
 // STFT constant tables, float64 math rounded to float32 (aec_tables.h)
 void build_dev_tables(DevTables& t) {
@@ -809,32 +853,26 @@ aec_status aec_stream_open(aec_handle* h, int32_t B) {
     if (B < 1) return fail(h, AEC_ERR_INVALID_ARG, "stream count must be >= 1");
     if (h->rescue.on) return fail(h, AEC_ERR_UNSUPPORTED, "the streaming kernels have no canceller rescue (aec_set_canceller_rescue)");
     AEC_ON_DEVICE(h);
-    HIP_TRY(h, hipDeviceSynchronize());   // a previous state may still be in use
-    if (h->d_state) { HIP_TRY(h, hipFree(h->d_state)); h->d_state = nullptr; }
-    h->stream_B = 0;
     const int64_t stride = stream_state_floats(h->cfg.nlms_taps, h->canc.kind);
-    HIP_TRY(h, hipMalloc(&h->d_state, (size_t)B * stride * sizeof(float)));
-    HIP_TRY(h, hipMemset(h->d_state, 0, (size_t)B * stride * sizeof(float)));
+    const aec_status s = state_open(h, h->d_state, h->stream_B, B, stride);
+    if (s != AEC_OK) return s;
+    h->stream_stride = stride;
     if (h->canc.kind == kCancellerKalman) {
+        h->stream_B = 0;                  // no stream to step until the covariances are in place
         HIP_TRY(h, launch_stream_cov_fill(h->d_state, stride, 0, B, h->cfg.nlms_taps, h->canc.p0, nullptr));
         HIP_TRY(h, hipStreamSynchronize(nullptr));
+        h->stream_B = B;
     }
-    h->stream_B = B;
-    h->stream_stride = stride;
     return AEC_OK;
 }
 
 aec_status aec_stream_reset(aec_handle* h, int32_t b, void* stream) {
     if (!h) return AEC_ERR_INVALID_ARG;
-    if (!h->d_state) return fail(h, AEC_ERR_INVALID_ARG, "aec_stream_open first");
-    if (b < -1 || b >= h->stream_B) return fail(h, AEC_ERR_INVALID_ARG, "stream index out of range");
+    const aec_status s = state_reset(h, h->d_state, h->stream_B, h->stream_stride, b, "aec_stream_open first", stream);
+    if (s != AEC_OK || h->canc.kind != kCancellerKalman) return s;
     AEC_ON_DEVICE(h);
-    const int64_t first = b < 0 ? 0 : b, count = b < 0 ? h->stream_B : 1;
-    HIP_TRY(h, hipMemsetAsync(h->d_state + first * h->stream_stride, 0, (size_t)count * h->stream_stride * sizeof(float),
-                              reinterpret_cast<hipStream_t>(stream)));
-    if (h->canc.kind == kCancellerKalman)
-        HIP_TRY(h, launch_stream_cov_fill(h->d_state, h->stream_stride, (int)first, (int)count, h->cfg.nlms_taps,
-                                          h->canc.p0, reinterpret_cast<hipStream_t>(stream)));
+    HIP_TRY(h, launch_stream_cov_fill(h->d_state, h->stream_stride, b < 0 ? 0 : b, b < 0 ? h->stream_B : 1, h->cfg.nlms_taps,
+                                      h->canc.p0, reinterpret_cast<hipStream_t>(stream)));
     return AEC_OK;
 }
 
@@ -1051,8 +1089,8 @@ aec_status aec_adam_step_multi(aec_handle* h, float* const* params, const float*
 
 // ---------------------------------------------------------------------------
 // Far-end bulk delay (kernels in aec_delay.hip).  Stateless: the host lengths ride in the kernel
-// arguments, kDelayRows streams per launch, so the calls use none of the handle's workspace and
-// take no part in the ordering of its other calls (begin_call / end_call) or in the look-ahead.
+// arguments (launch_row_batches), so the calls use none of the handle's workspace and take no
+// part in the ordering of its other calls (begin_call / end_call) or in the look-ahead.
 // ---------------------------------------------------------------------------
 aec_status aec_delay_estimate(aec_handle* h, const float* mic, const float* ref, const int64_t* lengths, int32_t B,
                               int64_t ld, int32_t max_lag, int32_t* delay, float* curve, void* stream) {
@@ -1063,12 +1101,9 @@ aec_status aec_delay_estimate(aec_handle* h, const float* mic, const float* ref,
     DelayArgs a{};
     a.mic = mic; a.ref = ref; a.ld = ld; a.tables = reinterpret_cast<const float*>(h->d_tab);
     a.delay = delay; a.curve = curve; a.max_lag = max_lag;
-    for (int32_t b0 = 0; b0 < B; b0 += kDelayRows) {
-        const int nb = std::min<int32_t>(kDelayRows, B - b0);
-        a.b0 = b0;
-        for (int i = 0; i < nb; ++i) a.len[i] = (int32_t)lengths[b0 + i];
-        HIP_TRY(h, launch_delay_estimate(a, nb, reinterpret_cast<hipStream_t>(stream)));
-    }
+    HIP_TRY(h, launch_row_batches(a, lengths, B, [&](const DelayArgs& x, int nb, int64_t) {
+        return launch_delay_estimate(x, nb, reinterpret_cast<hipStream_t>(stream));
+    }));
     return AEC_OK;
 }
 
@@ -1080,26 +1115,17 @@ aec_status aec_delay_apply(aec_handle* h, const float* ref, const int64_t* lengt
     AEC_ON_DEVICE(h);
     ShiftArgs a{};
     a.ref = ref; a.ld = ld; a.shift = shift; a.out = out; a.ld_out = ld_out;
-    for (int32_t b0 = 0; b0 < B; b0 += kDelayRows) {
-        const int nb = std::min<int32_t>(kDelayRows, B - b0);
-        a.b0 = b0;
-        int64_t nmax = 0;
-        for (int i = 0; i < nb; ++i) {
-            a.len[i] = (int32_t)lengths[b0 + i];
-            nmax = std::max(nmax, lengths[b0 + i]);
-        }
-        HIP_TRY(h, launch_delay_apply(a, nb, nmax, reinterpret_cast<hipStream_t>(stream)));
-    }
+    HIP_TRY(h, launch_row_batches(a, lengths, B, [&](const ShiftArgs& x, int nb, int64_t nmax) {
+        return launch_delay_apply(x, nb, nmax, reinterpret_cast<hipStream_t>(stream));
+    }));
     return AEC_OK;
 }
 
 // ---------------------------------------------------------------------------
 // Far-end clock drift (kernels in aec_drift.hip, checks in aec_host.h).  Stateless as the delay
-// calls above, with the same launches of kDelayRows rows; the resampler's table is the handle's
-// one piece of it, uploaded by aec_create.
+// calls above, with the same cut into launches; the resampler's table is the handle's one piece
+// of it, uploaded by aec_create.
 // ---------------------------------------------------------------------------
-static_assert(kDriftRows == kDelayRows, "one cut of a batch into launches for both");
-
 aec_status aec_drift_estimate(aec_handle* h, const float* mic, const float* ref, const int64_t* lengths, int32_t B,
                               int64_t ld, const int32_t* shift, int32_t seg_frames, float max_ppm, int32_t ngrid,
                               float* drift_ppm, float* curve, void* stream) {
@@ -1110,12 +1136,9 @@ aec_status aec_drift_estimate(aec_handle* h, const float* mic, const float* ref,
     DriftEstArgs a{};
     a.mic = mic; a.ref = ref; a.ld = ld; a.shift = shift; a.tables = reinterpret_cast<const float*>(h->d_tab);
     a.drift_ppm = drift_ppm; a.curve = curve; a.seg_frames = seg_frames; a.ngrid = ngrid; a.max_ppm = max_ppm;
-    for (int32_t b0 = 0; b0 < B; b0 += kDriftRows) {
-        const int nb = std::min<int32_t>(kDriftRows, B - b0);
-        a.b0 = b0;
-        for (int i = 0; i < nb; ++i) a.len[i] = (int32_t)lengths[b0 + i];
-        HIP_TRY(h, launch_drift_estimate(a, nb, reinterpret_cast<hipStream_t>(stream)));
-    }
+    HIP_TRY(h, launch_row_batches(a, lengths, B, [&](const DriftEstArgs& x, int nb, int64_t) {
+        return launch_drift_estimate(x, nb, reinterpret_cast<hipStream_t>(stream));
+    }));
     return AEC_OK;
 }
 
@@ -1128,16 +1151,9 @@ aec_status aec_drift_apply(aec_handle* h, const float* ref, const int64_t* lengt
     DriftApplyArgs a{};
     a.ref = ref; a.ld = ld; a.shift = shift; a.drift_ppm = drift_ppm; a.table = h->d_drift_tab;
     a.out = out; a.ld_out = ld_out;
-    for (int32_t b0 = 0; b0 < B; b0 += kDriftRows) {
-        const int nb = std::min<int32_t>(kDriftRows, B - b0);
-        a.b0 = b0;
-        int64_t nmax = 0;
-        for (int i = 0; i < nb; ++i) {
-            a.len[i] = (int32_t)lengths[b0 + i];
-            nmax = std::max(nmax, lengths[b0 + i]);
-        }
-        HIP_TRY(h, launch_drift_apply(a, nb, nmax, reinterpret_cast<hipStream_t>(stream)));
-    }
+    HIP_TRY(h, launch_row_batches(a, lengths, B, [&](const DriftApplyArgs& x, int nb, int64_t nmax) {
+        return launch_drift_apply(x, nb, nmax, reinterpret_cast<hipStream_t>(stream));
+    }));
     return AEC_OK;
 }
 
@@ -1182,13 +1198,9 @@ aec_status aec_delay_track_open(aec_handle* h, int32_t B, const aec_delay_track_
     const Check c = check_delay_track_open(B, cfg->max_lag, cfg->period, cfg->hold, cfg->lead, cfg->forget, cfg->ratio);
     if (c.status != AEC_OK) return fail(h, c.status, c.why);
     AEC_ON_DEVICE(h);
-    HIP_TRY(h, hipDeviceSynchronize());   // a previous state may still be in use
-    if (h->d_track) { HIP_TRY(h, hipFree(h->d_track)); h->d_track = nullptr; }
-    h->track_B = 0;
     const int64_t stride = delay_track_state_floats(delay_track_cap(cfg->max_lag));
-    HIP_TRY(h, hipMalloc(&h->d_track, (size_t)B * stride * sizeof(float)));
-    HIP_TRY(h, hipMemset(h->d_track, 0, (size_t)B * stride * sizeof(float)));
-    h->track_B = B;
+    const aec_status s = state_open(h, h->d_track, h->track_B, B, stride);
+    if (s != AEC_OK) return s;
     h->track_stride = stride;
     h->track_cfg = *cfg;
     return AEC_OK;
@@ -1196,13 +1208,7 @@ aec_status aec_delay_track_open(aec_handle* h, int32_t B, const aec_delay_track_
 
 aec_status aec_delay_track_reset(aec_handle* h, int32_t b, void* stream) {
     if (!h) return AEC_ERR_INVALID_ARG;
-    if (!h->d_track) return fail(h, AEC_ERR_INVALID_ARG, "aec_delay_track_open first");
-    if (b < -1 || b >= h->track_B) return fail(h, AEC_ERR_INVALID_ARG, "stream index out of range");
-    AEC_ON_DEVICE(h);
-    const int64_t first = b < 0 ? 0 : b, count = b < 0 ? h->track_B : 1;
-    HIP_TRY(h, hipMemsetAsync(h->d_track + first * h->track_stride, 0, (size_t)count * h->track_stride * sizeof(float),
-                              reinterpret_cast<hipStream_t>(stream)));
-    return AEC_OK;
+    return state_reset(h, h->d_track, h->track_B, h->track_stride, b, "aec_delay_track_open first", stream);
 }
 
 aec_status aec_delay_track_push(aec_handle* h, const float* mic, const float* ref, int64_t ld_in, float* ref_out,
@@ -1240,26 +1246,15 @@ aec_status aec_drift_track_open(aec_handle* h, int32_t B, const aec_drift_track_
     const Check ck = check_drift_track_open(B, c);
     if (ck.status != AEC_OK) return fail(h, ck.status, ck.why);
     AEC_ON_DEVICE(h);
-    HIP_TRY(h, hipDeviceSynchronize());   // a previous state may still be in use
-    if (h->d_dtrack) { HIP_TRY(h, hipFree(h->d_dtrack)); h->d_dtrack = nullptr; }
-    h->dtrack_B = 0;
-    const size_t bytes = (size_t)B * kDriftTrackStateFloats * sizeof(float);
-    HIP_TRY(h, hipMalloc(&h->d_dtrack, bytes));
-    HIP_TRY(h, hipMemset(h->d_dtrack, 0, bytes));
-    h->dtrack_B = B;
+    const aec_status s = state_open(h, h->d_dtrack, h->dtrack_B, B, kDriftTrackStateFloats);
+    if (s != AEC_OK) return s;
     h->dtrack_cfg = c;
     return AEC_OK;
 }
 
 aec_status aec_drift_track_reset(aec_handle* h, int32_t b, void* stream) {
     if (!h) return AEC_ERR_INVALID_ARG;
-    if (!h->d_dtrack) return fail(h, AEC_ERR_INVALID_ARG, "aec_drift_track_open first");
-    if (b < -1 || b >= h->dtrack_B) return fail(h, AEC_ERR_INVALID_ARG, "stream index out of range");
-    AEC_ON_DEVICE(h);
-    const int64_t first = b < 0 ? 0 : b, count = b < 0 ? h->dtrack_B : 1;
-    HIP_TRY(h, hipMemsetAsync(h->d_dtrack + first * kDriftTrackStateFloats, 0,
-                              (size_t)count * kDriftTrackStateFloats * sizeof(float), reinterpret_cast<hipStream_t>(stream)));
-    return AEC_OK;
+    return state_reset(h, h->d_dtrack, h->dtrack_B, kDriftTrackStateFloats, b, "aec_drift_track_open first", stream);
 }
 
 aec_status aec_drift_track_push(aec_handle* h, const float* mic, const float* ref, int64_t ld_in, float* ref_out,

@@ -1,15 +1,17 @@
 // aec_delay.h — argument blocks and launchers of the far-end bulk-delay kernels (aec_delay.hip;
-// include/aec_hip.h aec_delay_estimate / aec_delay_apply).  Internal.
+// include/aec_hip.h aec_delay_estimate / aec_delay_apply).  Internal.  Everything above
+// the launchers is plain C++17 with no HIP in it (aec_drift.h, which a host compiler builds alone,
+// includes it for kFrontRows); the launchers are declared for HIP translation units only.
 #pragma once
-#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace aec {
 
-// Streams per launch: the host lengths ride in the kernel arguments (1 KiB of the 4 KiB a launch
-// may carry), so neither call keeps a device buffer in the handle or orders itself against the
-// handle's other calls; a larger batch is cut into launches of this many rows.
-constexpr int kDelayRows = 256;
+// Streams per launch of the stateless far-end calls, delay and drift (aec_drift.h) alike: the host
+// lengths ride in the kernel arguments (1 KiB of the 4 KiB a launch may carry), so no call keeps a
+// device buffer in the handle or orders itself against the handle's other calls; a larger batch is
+// cut into launches of this many rows (aec_api.hip launch_row_batches).
+constexpr int kFrontRows = 256;
 constexpr int kDelayMaxLag = 63;        // lags 0 .. 63: the largest ring the LDS holds
 constexpr int kDelayMaxShift = 64;      // aec_delay_apply clamps a shift to [0, 64] frames
 
@@ -22,7 +24,7 @@ struct DelayArgs {
     float* curve;            // [B][max_lag + 1] or null
     int32_t max_lag;
     int32_t b0;              // first stream of this launch (block i runs stream b0 + i)
-    int32_t len[kDelayRows]; // lengths of streams b0 ..
+    int32_t len[kFrontRows]; // lengths of streams b0 ..
 };
 
 struct ShiftArgs {
@@ -32,7 +34,7 @@ struct ShiftArgs {
     float* out;              // [B][ld_out]
     int64_t ld_out;
     int32_t b0;
-    int32_t len[kDelayRows];
+    int32_t len[kFrontRows];
 };
 
 // The streaming tracker (aec_delay_track_*).  Nothing per row comes from the host, so
@@ -63,11 +65,16 @@ struct TrackArgs {
     float forget, ratio;
 };
 
-// nb <= kDelayRows streams from a.b0; a.len[0 .. nb) filled by the caller
+}  // namespace aec
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+namespace aec {
+// nb <= kFrontRows streams from a.b0; a.len[0 .. nb) filled by the caller
 hipError_t launch_delay_estimate(const DelayArgs& a, int nb, hipStream_t st);
 // nmax: the longest of a.len[0 .. nb)
 hipError_t launch_delay_apply(const ShiftArgs& a, int nb, int64_t nmax, hipStream_t st);
 // one block per stream, B of them; the lag capacity (and with it the state layout) follows a.max_lag
 hipError_t launch_delay_track(const TrackArgs& a, int B, hipStream_t st);
-
 }  // namespace aec
+#endif

@@ -14,29 +14,23 @@
 //   correlate  thread k = bin k.  The ring keeps the last CAP - 1 far-end rows before the chunk and
 //              the chunk's own, so lane k reads each row once (its own column: consecutive lanes,
 //              consecutive 8-byte words, no bank conflict) and pairs it with every mic frame of the
-//              chunk it belongs to: acc[t - r] += M[t] conj(R[r]), one complex accumulator per lag
-//              in registers, every index static.
+//              chunk it belongs to: acc[t - r] += M[t] conj(R[r]) (cmac_conj), one complex
+//              accumulator per lag in registers, every index static.
 // P_k[d] has no accumulator per lag: `head` sums |R[r]|^2 over r <= T-1-max_lag as the rows pass,
 // and the last max_lag rows are still in the ring at the end, so P[max_lag] = head and
 // P[d] = P[d+1] + |R[T-1-d]|^2 (sums of non-negative terms only: no cancellation).
 // The order of every sum depends on the stream's own T and max_lag alone, so a stream's curve does
-// not depend on the batch, its row or the other rows.
+// not depend on the batch, its row or the other rows.  cmac_conj is aec_frontend.h's; the rest of
+// this kernel keeps its own text, because the 64-lag instantiation measured 3 % slower with the
+// shared transform_row (profiles/frontend_shared.txt).  The tracker below takes every shared step
+// (table staging, transform_row, staged_row, the lag score and its reduction) from that header.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "aec_delay.h"
-#include "aec_fft.h"
-#include "aec_stft.h"
-#include "aec_tables.h"
+#include "aec_frontend.h"
 
 namespace aec {
-
-// acc += m conj(r) as two packed FMAs (one VALU issue per pair of lanes' products, as the FFT core
-// of aec_fft.h): (m.x, m.y) r.x, then mi r.y with mi = -i m = (m.y, -m.x); r's half is picked by op_sel
-__device__ __forceinline__ void cmac_conj(pf2& acc, pf2 m, pf2 mi, pf2 r) {
-    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[1,0,1]" : "+v"(acc) : "v"(m), "v"(r));
-    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "+v"(acc) : "v"(mi), "v"(r));
-}
 
 template <int CAP, int CHUNK>
 struct DelayCfg {
@@ -44,7 +38,7 @@ struct DelayCfg {
     static constexpr int kTW = CHUNK / 4;             // transform waves per signal
     static constexpr int kRows = CAP - 1 + CHUNK;     // ring rows of 256 float2
     static constexpr size_t kBytes =
-        (258 * 2 + 256 * 2 + 512 + (size_t)2 * kTW * kWaveFloats + (size_t)kRows * 512) * sizeof(float);
+        (kFftTableFloats + (size_t)2 * kTW * kWaveFloats + (size_t)kRows * 512) * sizeof(float);
     static_assert(kBytes <= 160 * 1024, "LDS");
     static_assert(2 * kTW * kWaveFloats >= 5 * CAP, "the final reduction reuses the wave regions");
 };
@@ -224,15 +218,16 @@ __global__ __launch_bounds__(256) void delay_apply_kernel(ShiftArgs p) {
 //              LDS: a thread reads back from the ring exactly what it stored there, so no barrier
 //              orders the ring, and staging CAP rows in LDS (128 KiB at 64 lags) would buy 7 of 64
 //              row reads per hop at best.  The q ring is read on evaluation hops only.
-//   evaluate   the end phase above on hops with (t + 1) % period == 0, then the first maximiser
-//              by a shuffle reduction every wave runs for itself, so all threads hold the decision.
+//   evaluate   the end phase above (lag_score, lag_reduce, lag_sum) on hops with
+//              (t + 1) % period == 0, then the first maximiser by a shuffle reduction every wave
+//              runs for itself, so all threads hold the decision.
 // A hop's arithmetic is the same wherever the packet boundaries fall, and every sum's order is
 // fixed by the lag capacity alone: results do not depend on B, the row, the strides or the packets.
 // ---------------------------------------------------------------------------
 template <int CAP>
 struct TrackCfg {
     static constexpr int kChunk = 8;                  // hops per transform phase: 2 waves x 4 frames per signal
-    static constexpr size_t kBytes = (258 * 2 + 256 * 2 + 512 + (size_t)4 * kWaveFloats + 5 * CAP) * sizeof(float);
+    static constexpr size_t kBytes = (kFftTableFloats + (size_t)4 * kWaveFloats + 5 * CAP) * sizeof(float);
     static_assert(CAP % 16 == 0 && CAP <= 64, "lags go in batches of 16; a wave finds the maximiser of <= 64");
     static_assert(kBytes <= 64 * 1024, "LDS without opting in");
 };
@@ -241,29 +236,17 @@ template <int CAP>
 __global__ __launch_bounds__(256, 1) void delay_track_kernel(TrackArgs p) {
     constexpr int CH = TrackCfg<CAP>::kChunk;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float2* sTw512 = reinterpret_cast<float2*>(smem);                 // 258
-    float2* sTwT = sTw512 + 258;                                      // 256
-    float* sHann = reinterpret_cast<float*>(sTwT + 256);              // 512
-    float* sWave = sHann + 512;                                       // 4 * kWaveFloats
+    FftTables tabs;
+    float* sWave = carve_fft_tables(smem, tabs);                      // 4 * kWaveFloats
     float* sRed = sWave + 4 * kWaveFloats;                            // [CAP][4]
     float* sCurve = sRed + 4 * CAP;                                   // [CAP]
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int gg = lane >> 4, lb = lane & 15;
     const int64_t b = blockIdx.x;
-    int cnt = p.max_hops;
-    if (p.hops) {
-        const int h = p.hops[b];
-        cnt = h < 0 ? 0 : (h > p.max_hops ? p.max_hops : h);
-    }
+    const int cnt = packet_hops(p.hops, b, p.max_hops);
     if (cnt == 0) return;                                             // nothing of this stream changes
-
-    const DevTables* tb = reinterpret_cast<const DevTables*>(p.tables);
-    sTwT[tid] = tb->twT[tid];
-    sTw512[tid] = tb->tw512[tid];
-    if (tid < 2) sTw512[256 + tid] = tb->tw512[256 + tid];
-    sHann[tid] = tb->hann[tid];
-    sHann[tid + 256] = tb->hann[tid + 256];
+    stage_fft_tables(p.tables, tabs, tid);
 
     float* st = p.state + b * p.state_stride;
     float2* gC = reinterpret_cast<float2*>(st);                       // [CAP][256]
@@ -318,21 +301,7 @@ __global__ __launch_bounds__(256, 1) void delay_track_kernel(TrackArgs p) {
             wave_commit(wr, pf, 0.f, n, wt, lane);
             if (wt == 0) *reinterpret_cast<float4*>(wr + 4 * lane) = prev;
             if (wt + CH < cnt) wave_prefetch(pf, row, n, wt + CH, lane, al);
-            wave_fence();
-            float2 v[16];
-            load_frame(v, wr, sHann, gg, lb);
-            wave_fence();                                             // samples read before scratch reuse
-            fft256<false>(v, lb, scr, sTwT);
-            float2 xa[8], xb[8], x128;
-            rfft_unpack(v, lb, sTw512, xa, xb, x128);
-            float2* dst = reinterpret_cast<float2*>(scr);
-#pragma unroll
-            for (int m = 0; m < 8; ++m) {
-                const int kk = lb + 16 * m;
-                dst[kk] = xa[m];                                      // slot 0 holds DC: left out of S
-                if (kk) dst[256 - kk] = xb[m];
-            }
-            if (lb == 0) dst[128] = x128;
+            transform_row(wr, scr, reinterpret_cast<float2*>(scr), tabs, gg, lb);
         }
         __syncthreads();
         const int nch = cnt - c0 < CH ? cnt - c0 : CH;
@@ -346,9 +315,7 @@ __global__ __launch_bounds__(256, 1) void delay_track_kernel(TrackArgs p) {
             if (src >= 0) ao = refrow[(int64_t)src * kHop + k];
             else if (t0 + src >= 0) ao = gSamp[((t0 + src) & 63) * 256 + k];
 
-            const float2 mv = reinterpret_cast<const float2*>(sWave + (i >> 2) * kWaveFloats + (i & 3) * kGroupFloats)[k];
-            const float2 rv =
-                reinterpret_cast<const float2*>(sWave + (2 + (i >> 2)) * kWaveFloats + (i & 3) * kGroupFloats)[k];
+            const float2 mv = staged_row(sWave, i, k), rv = staged_row(sWave + kFarRows, i, k);
             q = fmaf(p.forget, q, fmaf(rv.x, rv.x, rv.y * rv.y));
             gR[slot * 256 + k] = rv;
             gQ[slot * 256 + k] = q;
@@ -395,16 +362,14 @@ __global__ __launch_bounds__(256, 1) void delay_track_kernel(TrackArgs p) {
                         static_for<0, 16>([&](auto ui) {
                             constexpr int u = decltype(ui)::value, d = 16 * g + u;
                             float sv = 0.f;
-                            if (k >= 1) sv = fmaf(acc[d].x, acc[d].x, acc[d].y * acc[d].y) / (pw[u] + 1e-6f);
-#pragma unroll
-                            for (int o = 32; o > 0; o >>= 1) sv += __shfl_xor(sv, o);
-                            if (lane == 0) sRed[4 * d + wave] = sv;
+                            if (k >= 1) sv = lag_score(acc[d], pw[u]);
+                            lag_reduce(sRed, d, sv, wave, lane);
                         });
                     }
                 });
                 __syncthreads();
                 if (tid <= max_lag) {
-                    sLast = (sRed[4 * tid] + sRed[4 * tid + 1]) + (sRed[4 * tid + 2] + sRed[4 * tid + 3]);
+                    sLast = lag_sum(sRed, tid);
                     sCurve[tid] = sLast;
                 }
                 __syncthreads();
@@ -477,7 +442,7 @@ static hipError_t launch_delay_cap(const DelayArgs& a, int nb, hipStream_t st) {
 
 hipError_t launch_delay_estimate(const DelayArgs& a, int nb, hipStream_t st) {
     if (nb <= 0) return hipSuccess;
-    if (nb > kDelayRows || a.max_lag < 0 || a.max_lag > kDelayMaxLag) return hipErrorInvalidValue;
+    if (nb > kFrontRows || a.max_lag < 0 || a.max_lag > kDelayMaxLag) return hipErrorInvalidValue;
     // lag capacity 16 / 32 / 48 / 64: a short search does not carry 64 lags of accumulators; the 64-lag
     // ring leaves LDS for two transform waves (chunks of 4 frames), the others for four (8 frames)
     if (a.max_lag < 16) return launch_delay_cap<16, 8>(a, nb, st);
@@ -506,7 +471,7 @@ hipError_t launch_delay_track(const TrackArgs& a, int B, hipStream_t st) {
 
 hipError_t launch_delay_apply(const ShiftArgs& a, int nb, int64_t nmax, hipStream_t st) {
     if (nb <= 0 || nmax <= 0) return hipSuccess;
-    if (nb > kDelayRows) return hipErrorInvalidValue;
+    if (nb > kFrontRows) return hipErrorInvalidValue;
     hipLaunchKernelGGL(delay_apply_kernel, dim3((unsigned)((nmax + 1023) / 1024), nb), dim3(256), 0, st, a);
     return hipGetLastError();
 }

@@ -9,10 +9,10 @@
 #include <cmath>
 #include <vector>
 
+#include "aec_delay.h"      // kFrontRows: streams per launch, the host lengths ride in the kernel arguments
+
 namespace aec {
 
-// Streams per launch: the host lengths ride in the kernel arguments, as in aec_delay.h
-constexpr int kDriftRows = 256;             // == kDelayRows (aec_api.hip asserts it)
 constexpr int kDriftMaxShift = 64;          // frames, aec_delay_apply's clamp
 constexpr int kDriftSegMin = 4, kDriftSegMax = 64;      // seg_frames
 constexpr float kDriftMaxPpm = 2000.f;      // the search's and the resampler's limit
@@ -97,7 +97,7 @@ struct DriftEstArgs {
     int32_t seg_frames, ngrid;
     float max_ppm;
     int32_t b0;              // first stream of this launch (block i runs stream b0 + i)
-    int32_t len[kDriftRows]; // lengths of streams b0 ..
+    int32_t len[kFrontRows]; // lengths of streams b0 ..
 };
 
 struct DriftApplyArgs {
@@ -109,7 +109,7 @@ struct DriftApplyArgs {
     float* out;              // [B][ld_out]
     int64_t ld_out;
     int32_t b0;
-    int32_t len[kDriftRows];
+    int32_t len[kFrontRows];
 };
 
 }  // namespace aec
@@ -117,7 +117,7 @@ struct DriftApplyArgs {
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 namespace aec {
-// nb <= kDriftRows streams from a.b0; a.len[0 .. nb) filled by the caller
+// nb <= kFrontRows streams from a.b0; a.len[0 .. nb) filled by the caller
 hipError_t launch_drift_estimate(const DriftEstArgs& a, int nb, hipStream_t st);
 // nmax: the longest of a.len[0 .. nb)
 hipError_t launch_drift_apply(const DriftApplyArgs& a, int nb, int64_t nmax, hipStream_t st);

@@ -13,49 +13,39 @@
 //
 // One block of four waves per stream walks it once in chunks of 8 frames, two phases per chunk:
 //   transform  waves 0, 1 the mic frames t0 .. t0+7, waves 2, 3 the ref frames t0 - s_b .. +7, one
-//              16-lane group per frame (aec_stft.h / aec_fft.h).  No ring: the far-end row paired
+//              16-lane group per frame (transform_row, aec_frontend.h).  No ring: the far-end row paired
 //              with mic frame t is the transform of ref frame t - s_b, loaded at that offset, and
 //              the buffer range check supplies the zeros in front of the stream.  Both rows of a
 //              frame stay in the group's own LDS scratch.
-//   correlate  thread k = bin k: C_s in a register pair, one packed conj-MAC per frame, and at
-//              each segment edge one PHAT step into D (registers).
-// Then D goes to LDS, thread g evaluates J[g] over k = 1..255 in order (the phase k u_g reduced
-// to its fractional part in float64 before the sine and cosine), and wave 0 picks the first
-// maximiser and forms the parabola.  The order of every sum depends on T, S and ngrid alone, so
-// a stream's result does not depend on the batch, its row or the other rows.
+//   correlate  thread k = bin k: C_s in a register pair, one packed conj-MAC per frame (cmac_conj),
+//              and at each segment edge one PHAT step into D (phat_step; registers).
+// Then D goes to LDS, thread g evaluates J[g] over k = 1..255 in order (drift_curve_point: the
+// phase k u_g reduced to its fractional part in float64 before the sine and cosine), and wave 0
+// picks the first maximiser and forms the parabola (drift_peak).  The order of every sum depends
+// on T, S and ngrid alone, so a stream's result does not depend on the batch, its row or the other
+// rows.  The helpers named are aec_frontend.h's: drift_track_kernel runs the very same ones.
 //
 // Resampler: one block per (stream, tile of kDriftTile outputs).  The table and the tile's input
 // window go to LDS (dword loads, lane i sample i: coalesced for any ld and alignment; zeros
 // outside [0, n)), then thread i of each run of 256 outputs forms its position in float64 exactly
-// as the header writes it, blends rows ph and ph + 1 and sums the 32 taps in order.
+// as the header writes it, blends rows ph and ph + 1 and sums the 32 taps in order (drift_interp).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "aec_drift.h"
-#include "aec_fft.h"
-#include "aec_stft.h"
-#include "aec_tables.h"
+#include "aec_frontend.h"
 
 namespace aec {
 
-// acc += m conj(r) as two packed FMAs: (m.x, m.y) r.x, then mi r.y with mi = -i m = (m.y, -m.x);
-// r's half is picked by op_sel (the packed conj-MAC of aec_delay.hip)
-__device__ __forceinline__ void drift_cmac_conj(pf2& acc, pf2 m, pf2 mi, pf2 r) {
-    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[1,0,1]" : "+v"(acc) : "v"(m), "v"(r));
-    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "+v"(acc) : "v"(mi), "v"(r));
-}
-
 constexpr int kDriftChunk = 8;            // frames per transform phase: 2 waves x 4 frames per signal
-constexpr size_t kDriftEstBytes = (258 * 2 + 256 * 2 + 512 + (size_t)4 * kWaveFloats + 512 + 256) * sizeof(float);
+constexpr size_t kDriftEstBytes = (kFftTableFloats + (size_t)4 * kWaveFloats + 512 + 256) * sizeof(float);
 static_assert(kDriftEstBytes <= 64 * 1024, "LDS without opting in");
 
 __global__ __launch_bounds__(256, 1) void drift_estimate_kernel(DriftEstArgs p) {
     constexpr int CH = kDriftChunk;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float2* sTw512 = reinterpret_cast<float2*>(smem);                 // 258
-    float2* sTwT = sTw512 + 258;                                      // 256
-    float* sHann = reinterpret_cast<float*>(sTwT + 256);              // 512
-    float* sWave = sHann + 512;                                       // 4 * kWaveFloats
+    FftTables tabs;
+    float* sWave = carve_fft_tables(smem, tabs);                      // 4 * kWaveFloats
     float2* sD = reinterpret_cast<float2*>(sWave + 4 * kWaveFloats);  // 256
     float* sJ = reinterpret_cast<float*>(sD + 256);                   // 256
 
@@ -72,12 +62,7 @@ __global__ __launch_bounds__(256, 1) void drift_estimate_kernel(DriftEstArgs p) 
         if (tid == 0) p.drift_ppm[b] = 0.f;
         return;
     }
-    const DevTables* tb = reinterpret_cast<const DevTables*>(p.tables);
-    sTwT[tid] = tb->twT[tid];
-    sTw512[tid] = tb->tw512[tid];
-    if (tid < 2) sTw512[256 + tid] = tb->tw512[256 + tid];
-    sHann[tid] = tb->hann[tid];
-    sHann[tid + 256] = tb->hann[tid + 256];
+    stage_fft_tables(p.tables, tabs, tid);
     int sb = 0;
     if (p.shift) {
         sb = __builtin_amdgcn_readfirstlane(p.shift[b]);
@@ -103,38 +88,15 @@ __global__ __launch_bounds__(256, 1) void drift_estimate_kernel(DriftEstArgs p) 
             const int wt = t0 + foff;
             wave_commit(wr, pf, 0.f, n, wt, lane);
             if (t0 + CH < Tend) wave_prefetch(pf, row, n, wt + CH, lane, al);
-            wave_fence();
-            float2 v[16];
-            load_frame(v, wr, sHann, gg, lb);
-            wave_fence();                                             // samples read before scratch reuse
-            fft256<false>(v, lb, scr, sTwT);
-            float2 xa[8], xb[8], x128;
-            rfft_unpack(v, lb, sTw512, xa, xb, x128);
-            float2* dst = reinterpret_cast<float2*>(scr);
-#pragma unroll
-            for (int m = 0; m < 8; ++m) {
-                const int kk = lb + 16 * m;
-                dst[kk] = xa[m];                                      // slot 0 holds DC: left out of J
-                if (kk) dst[256 - kk] = xb[m];
-            }
-            if (lb == 0) dst[128] = x128;
+            transform_row(wr, scr, reinterpret_cast<float2*>(scr), tabs, gg, lb);
         }
         __syncthreads();
         const int nch = Tend - t0 < CH ? Tend - t0 : CH;
         for (int i = 0; i < nch; ++i) {
-            const float2 mv = reinterpret_cast<const float2*>(sWave + (i >> 2) * kWaveFloats + (i & 3) * kGroupFloats)[k];
-            const float2 rv =
-                reinterpret_cast<const float2*>(sWave + (2 + (i >> 2)) * kWaveFloats + (i & 3) * kGroupFloats)[k];
-            drift_cmac_conj(C, pf2{mv.x, mv.y}, pf2{mv.y, -mv.x}, pf2{rv.x, rv.y});
+            const float2 mv = staged_row(sWave, i, k), rv = staged_row(sWave + kFarRows, i, k);
+            cmac_conj(C, pf2{mv.x, mv.y}, pf2{mv.y, -mv.x}, pf2{rv.x, rv.y});
             if (++fs == S) {                                          // segment edge: one PHAT step
-                if (seg > 0) {
-                    // Z = C conj(Cp)
-                    const float zx = fmaf(C.x, Cp.x, C.y * Cp.y);
-                    const float zy = fmaf(C.y, Cp.x, -(C.x * Cp.y));
-                    const float nz = sqrtf(fmaf(zx, zx, zy * zy) + 1e-30f);
-                    D.x += zx / nz;
-                    D.y += zy / nz;
-                }
+                if (seg > 0) phat_step(D, C, Cp);
                 Cp = C;
                 C = pf2{0.f, 0.f};
                 fs = 0;
@@ -147,57 +109,14 @@ __global__ __launch_bounds__(256, 1) void drift_estimate_kernel(DriftEstArgs p) 
     sD[k] = k >= 1 ? make_float2(D.x, D.y) : make_float2(0.f, 0.f);
     __syncthreads();
     if (tid < ngrid) {
-        const double u = drift_cycles_per_bin(drift_grid_ppm(tid, ngrid, p.max_ppm), S);
-        float J = 0.f;
-        for (int kk = 1; kk < 256; ++kk) {
-            double x = (double)kk * u;
-            x -= rint(x);                                             // k u_g mod 1, in [-1/2, 1/2]
-            float sn, cs;
-            sincospif(2.f * (float)x, &sn, &cs);
-            const float2 d = sD[kk];                                  // one address per wave: a broadcast
-            J = fmaf(d.x, cs, J);
-            J = fmaf(-d.y, sn, J);
-        }
+        const float J = drift_curve_point(sD, tid, ngrid, p.max_ppm, S);
         sJ[tid] = J;
         if (p.curve) p.curve[(int64_t)b * ngrid + tid] = J;
     }
     __syncthreads();
     if (wave == 0) {
-        // the first maximiser: each lane over its own candidates in rising order, then across lanes
-        float bv = 0.f;
-        int best = 256;
-        bool any = false;
-        for (int g = lane; g < ngrid; g += 64) {
-            const float v = sJ[g];
-            any |= v != 0.f;
-            if (best == 256 || v > bv) {
-                bv = v;
-                best = g;
-            }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(bv, o);
-            const int oi = __shfl_xor(best, o);
-            const bool take = oi < 256 && (best == 256 || ov > bv || (ov == bv && oi < best));
-            bv = take ? ov : bv;
-            best = take ? oi : best;
-        }
-        any = __any(any);
-        if (lane == 0) {
-            const int G = (ngrid - 1) / 2;
-            float off = 0.f;
-            if (best > 0 && best < ngrid - 1) {
-                const float y0 = sJ[best - 1], y1 = sJ[best], y2 = sJ[best + 1];
-                const float den = (y0 - y1) + (y2 - y1);
-                if (den < 0.f) {
-                    off = 0.5f * (y0 - y2) / den;
-                    off = off < -0.5f ? -0.5f : (off > 0.5f ? 0.5f : off);
-                }
-            }
-            const float step = p.max_ppm / (float)G;
-            p.drift_ppm[b] = any ? ((float)(best - G) + off) * step : 0.f;
-        }
+        const float r = drift_peak(sJ, ngrid, p.max_ppm, lane);
+        if (lane == 0) p.drift_ppm[b] = r;
     }
 }
 
@@ -245,29 +164,13 @@ __global__ __launch_bounds__(256) void drift_apply_kernel(DriftApplyArgs p) {
         const double pos = __dsub_rn(__dmul_rn((double)i, q), back);
         const double fl = floor(pos);
         const float fr = (float)__dsub_rn(pos, fl);
-        const float u = 256.f * fr;
-        int ph = (int)u;
-        ph = ph > kDriftPhases - 1 ? kDriftPhases - 1 : ph;
-        const float a = u - (float)ph, a1 = 1.f - a;
-        const float4* h0 = reinterpret_cast<const float4*>(sTab + ph * kDriftTaps);
-        const float4* h1 = h0 + kDriftTaps / 4;
-        const float* x = sWin + ((int)fl + kDriftTapLo - w0);         // in [0, kDriftWindow - 32]: aec_drift.h
-        float acc = 0.f;
-#pragma unroll
-        for (int j4 = 0; j4 < kDriftTaps / 4; ++j4) {
-            const float4 c0 = h0[j4], c1 = h1[j4];
-            acc = fmaf(x[4 * j4 + 0], fmaf(a1, c0.x, a * c1.x), acc);
-            acc = fmaf(x[4 * j4 + 1], fmaf(a1, c0.y, a * c1.y), acc);
-            acc = fmaf(x[4 * j4 + 2], fmaf(a1, c0.z, a * c1.z), acc);
-            acc = fmaf(x[4 * j4 + 3], fmaf(a1, c0.w, a * c1.w), acc);
-        }
-        dst[i] = acc;
+        dst[i] = drift_interp(sTab, sWin, (int)fl + kDriftTapLo - w0, fr);   // offset in [0, kDriftWindow - 32]: aec_drift.h
     }
 }
 
 hipError_t launch_drift_estimate(const DriftEstArgs& a, int nb, hipStream_t st) {
     if (nb <= 0) return hipSuccess;
-    if (nb > kDriftRows || a.seg_frames < kDriftSegMin || a.seg_frames > kDriftSegMax || a.ngrid < kDriftGridMin ||
+    if (nb > kFrontRows || a.seg_frames < kDriftSegMin || a.seg_frames > kDriftSegMax || a.ngrid < kDriftGridMin ||
         a.ngrid > kDriftGridMax || a.ngrid % 2 == 0)
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(drift_estimate_kernel, dim3(nb), dim3(256), kDriftEstBytes, st, a);
@@ -276,7 +179,7 @@ hipError_t launch_drift_estimate(const DriftEstArgs& a, int nb, hipStream_t st) 
 
 hipError_t launch_drift_apply(const DriftApplyArgs& a, int nb, int64_t nmax, hipStream_t st) {
     if (nb <= 0 || nmax <= 0) return hipSuccess;
-    if (nb > kDriftRows) return hipErrorInvalidValue;
+    if (nb > kFrontRows) return hipErrorInvalidValue;
     hipLaunchKernelGGL(drift_apply_kernel, dim3((unsigned)((nmax + kDriftTile - 1) / kDriftTile), nb), dim3(256),
                        kDriftApplyBytes, st, a);
     return hipGetLastError();

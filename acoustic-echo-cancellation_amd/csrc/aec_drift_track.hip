@@ -5,8 +5,9 @@
 // Per stream and hop h (aec_hip.h has the definition in full): the rate q from the current ppm,
 // the anchor moved or re-centred (drift_track_advance, aec_drift_track.h: the code the host test
 // runs), 256 outputs resampled at p = A + (i - iA) q with aec_drift_apply's table, blend and tap
-// order, and C[k] += M[h,k] conj(O[h - s, k]) with O the spectrum of the *output* frames.  Every S
-// hops one PHAT step into D; every `pairs` of those J, its peak r, and ppm += gain r.
+// order (drift_interp), and C[k] += M[h,k] conj(O[h - s, k]) with O the spectrum of the *output*
+// frames.  Every S hops one PHAT step into D; every `pairs` of those J, its peak r, and
+// ppm += gain r.  Each step shared with aec_drift.hip is one function of aec_frontend.h.
 //
 // One block of four waves per stream advances it by a packet of hops, in chunks that end at the
 // next segment edge (min(8, hops left, S - fs)): the rate is constant inside a chunk.  Per chunk:
@@ -16,13 +17,13 @@
 //              and is rewritten only at the end of the launch.  Thread j forms output j of every
 //              hop, to ref_out and to an LDS copy of the chunk's output hops.
 //   transform  waves 0, 1 the mic frames, waves 2, 3 the output frames h - s, one 16-lane group
-//              per frame (aec_stft.h / aec_fft.h).  An output hop of this chunk comes from the LDS
-//              copy; an older one from the output ring in HBM (65 hops).
-//   correlate  thread k = bin k: C in a register pair, one packed conj-MAC per hop; the chunk's
-//              output hops then go into the ring (after the transform: with s = 63 their slots
-//              still held hops the transform needed), and at a segment edge the PHAT step, and
-//              when due the evaluation exactly as drift_estimate_kernel's, every wave finding the
-//              maximiser for itself so that all threads hold the new rate.
+//              per frame (transform_row).  An output hop of this chunk comes from the LDS copy; an
+//              older one from the output ring in HBM (65 hops).
+//   correlate  thread k = bin k: C in a register pair, one packed conj-MAC per hop (cmac_conj); the
+//              chunk's output hops then go into the ring (after the transform: with s = 63 their
+//              slots still held hops the transform needed), and at a segment edge phat_step, and
+//              when due drift_estimate_kernel's evaluation (drift_curve_point, drift_peak), every
+//              wave finding the maximiser for itself so that all threads hold the new rate.
 // Thread k owns column k of C, Cp, D and J in HBM and reads back only what it stored.  The output
 // ring is different: thread j writes sample j of a hop and a transform group reads the hop in a
 // later chunk of the same launch, so a block-scope fence and the barrier that ends a chunk order
@@ -32,18 +33,9 @@
 #include <stdint.h>
 
 #include "aec_drift_track.h"
-#include "aec_fft.h"
-#include "aec_stft.h"
-#include "aec_tables.h"
+#include "aec_frontend.h"
 
 namespace aec {
-
-// acc += m conj(r) as two packed FMAs: (m.x, m.y) r.x, then mi r.y with mi = -i m = (m.y, -m.x);
-// r's half is picked by op_sel (the packed conj-MAC of aec_delay.hip and aec_drift.hip)
-__device__ __forceinline__ void dtrack_cmac_conj(pf2& acc, pf2 m, pf2 mi, pf2 r) {
-    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[1,0,1]" : "+v"(acc) : "v"(m), "v"(r));
-    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "+v"(acc) : "v"(mi), "v"(r));
-}
 
 // The interpolation table (32.1 KiB, shared by every block, L2-resident) is read from global memory:
 // measured against a copy in LDS per block it is 1.6-2.5 us faster per call for one hop and within the
@@ -58,20 +50,18 @@ constexpr int kDtWin = kDriftTrackWindow;
 constexpr int kDtTabLds = AEC_DTRACK_TABLE_GLOBAL ? 0 : kDriftTableFloats;
 // FFT tables, four waves' scratch, the chunk's input windows and output hops, D and J: 63.0 KiB
 // (95.1 KiB with the table's copy, which launch_drift_track then opts in to)
-constexpr size_t kDriftTrackLds = (258 * 2 + 256 * 2 + 512 + (size_t)4 * kWaveFloats + kDtTabLds +
-                                   (size_t)kDtCh * kDtWin + (size_t)kDtCh * 256 + 512 + 256) * sizeof(float);
+constexpr size_t kDriftTrackLds = (kFftTableFloats + (size_t)4 * kWaveFloats + kDtTabLds + (size_t)kDtCh * kDtWin +
+                                   (size_t)kDtCh * 256 + 512 + 256) * sizeof(float);
 static_assert(kDriftTrackLds <= 160 * 1024, "LDS of one CU");
-static_assert((258 * 2 + 256 * 2 + 512 + 4 * kWaveFloats) % 4 == 0 && kDriftTableFloats % 4 == 0 && (kDtCh * kDtWin) % 4 == 0,
+static_assert((kFftTableFloats + 4 * kWaveFloats) % 4 == 0 && kDriftTableFloats % 4 == 0 && (kDtCh * kDtWin) % 4 == 0,
               "float4 rows in LDS");
 static_assert(kDtCh == 8, "2 waves x 4 frames per signal");
 
 __global__ __launch_bounds__(256, 1) void drift_track_kernel(DriftTrackArgs p) {
     constexpr int CH = kDtCh;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float2* sTw512 = reinterpret_cast<float2*>(smem);                 // 258
-    float2* sTwT = sTw512 + 258;                                      // 256
-    float* sHann = reinterpret_cast<float*>(sTwT + 256);              // 512
-    float* sWave = sHann + 512;                                       // 4 * kWaveFloats
+    FftTables tabs;
+    float* sWave = carve_fft_tables(smem, tabs);                      // 4 * kWaveFloats
     float* sTabLds = sWave + 4 * kWaveFloats;                         // the table's copy, when built with one
     const float* tab = AEC_DTRACK_TABLE_GLOBAL ? p.table : sTabLds;  // [257][32]
     float* sWin = sTabLds + kDtTabLds;                                // [CH][kDtWin]
@@ -82,19 +72,9 @@ __global__ __launch_bounds__(256, 1) void drift_track_kernel(DriftTrackArgs p) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int gg = lane >> 4, lb = lane & 15;
     const int64_t b = blockIdx.x;
-    int cnt = p.max_hops;
-    if (p.hops) {
-        const int h = p.hops[b];
-        cnt = h < 0 ? 0 : (h > p.max_hops ? p.max_hops : h);
-    }
+    const int cnt = packet_hops(p.hops, b, p.max_hops);
     if (cnt == 0) return;                                             // nothing of this stream changes
-
-    const DevTables* tb = reinterpret_cast<const DevTables*>(p.tables);
-    sTwT[tid] = tb->twT[tid];
-    sTw512[tid] = tb->tw512[tid];
-    if (tid < 2) sTw512[256 + tid] = tb->tw512[256 + tid];
-    sHann[tid] = tb->hann[tid];
-    sHann[tid + 256] = tb->hann[tid + 256];
+    stage_fft_tables(p.tables, tabs, tid);
     if (!AEC_DTRACK_TABLE_GLOBAL) {
         const float4* g4 = reinterpret_cast<const float4*>(p.table);
         float4* s4 = reinterpret_cast<float4*>(sTabLds);
@@ -199,22 +179,7 @@ __global__ __launch_bounds__(256, 1) void drift_track_kernel(DriftTrackArgs p) {
         static_for<0, CH>([&](auto ii) {
             constexpr int i = decltype(ii)::value;
             if (i < n) {
-                const float u = 256.f * wfr[i];
-                int ph = (int)u;
-                ph = ph > kDriftPhases - 1 ? kDriftPhases - 1 : ph;
-                const float a = u - (float)ph, a1 = 1.f - a;
-                const float4* h0 = reinterpret_cast<const float4*>(tab + ph * kDriftTaps);
-                const float4* h1 = h0 + kDriftTaps / 4;
-                const float* x = sWin + i * kDtWin + woff[i];
-                float acc = 0.f;
-#pragma unroll
-                for (int j4 = 0; j4 < kDriftTaps / 4; ++j4) {
-                    const float4 c0v = h0[j4], c1v = h1[j4];
-                    acc = fmaf(x[4 * j4 + 0], fmaf(a1, c0v.x, a * c1v.x), acc);
-                    acc = fmaf(x[4 * j4 + 1], fmaf(a1, c0v.y, a * c1v.y), acc);
-                    acc = fmaf(x[4 * j4 + 2], fmaf(a1, c0v.z, a * c1v.z), acc);
-                    acc = fmaf(x[4 * j4 + 3], fmaf(a1, c0v.w, a * c1v.w), acc);
-                }
+                const float acc = drift_interp(tab, sWin + i * kDtWin, woff[i], wfr[i]);
                 sOut[i * 256 + tid] = acc;
                 outrow[(int64_t)(c0 + i) * kHop + tid] = acc;
             }
@@ -244,30 +209,14 @@ __global__ __launch_bounds__(256, 1) void drift_track_kernel(DriftTrackArgs p) {
                 }
                 *reinterpret_cast<float4*>(wr + u * kHopStride + 4 * lane) = v;
             }
-            wave_fence();
-            float2 v[16];
-            load_frame(v, wr, sHann, gg, lb);
-            wave_fence();                                             // samples read before scratch reuse
-            fft256<false>(v, lb, scr, sTwT);
-            float2 xa[8], xb[8], x128;
-            rfft_unpack(v, lb, sTw512, xa, xb, x128);
-            float2* dst = reinterpret_cast<float2*>(scr);
-#pragma unroll
-            for (int m = 0; m < 8; ++m) {
-                const int kk = lb + 16 * m;
-                dst[kk] = xa[m];                                      // slot 0 holds DC: left out of J
-                if (kk) dst[256 - kk] = xb[m];
-            }
-            if (lb == 0) dst[128] = x128;
+            transform_row(wr, scr, reinterpret_cast<float2*>(scr), tabs, gg, lb);
         }
         __syncthreads();
 
         // ---- step 4, correlate; the chunk's output hops into the ring
         for (int i = 0; i < n; ++i) {
-            const float2 mv = reinterpret_cast<const float2*>(sWave + (i >> 2) * kWaveFloats + (i & 3) * kGroupFloats)[k];
-            const float2 rv =
-                reinterpret_cast<const float2*>(sWave + (2 + (i >> 2)) * kWaveFloats + (i & 3) * kGroupFloats)[k];
-            dtrack_cmac_conj(C, pf2{mv.x, mv.y}, pf2{mv.y, -mv.x}, pf2{rv.x, rv.y});
+            const float2 mv = staged_row(sWave, i, k), rv = staged_row(sWave + kFarRows, i, k);
+            cmac_conj(C, pf2{mv.x, mv.y}, pf2{mv.y, -mv.x}, pf2{rv.x, rv.y});
             gOut[((hc + i) % kDriftTrackOutHops) * 256 + tid] = sOut[i * 256 + tid];
         }
         fs += n;
@@ -277,12 +226,7 @@ __global__ __launch_bounds__(256, 1) void drift_track_kernel(DriftTrackArgs p) {
         if (fs == S) {
             fs = 0;
             if (have_prev) {
-                // Z = C conj(Cp)
-                const float zx = fmaf(C.x, Cp.x, C.y * Cp.y);
-                const float zy = fmaf(C.y, Cp.x, -(C.x * Cp.y));
-                const float nz = sqrtf(fmaf(zx, zx, zy * zy) + 1e-30f);
-                D.x += zx / nz;
-                D.y += zy / nz;
+                phat_step(D, C, Cp);
                 ++npairs;
             }
             Cp = C;
@@ -292,55 +236,11 @@ __global__ __launch_bounds__(256, 1) void drift_track_kernel(DriftTrackArgs p) {
                 sD[k] = k >= 1 ? make_float2(D.x, D.y) : make_float2(0.f, 0.f);
                 __syncthreads();
                 if (tid < ngrid) {
-                    const double u = drift_cycles_per_bin(drift_grid_ppm(tid, ngrid, p.cfg.max_ppm), S);
-                    float J = 0.f;
-                    for (int kk = 1; kk < 256; ++kk) {
-                        double x = (double)kk * u;
-                        x -= rint(x);                                 // k u_g mod 1, in [-1/2, 1/2]
-                        float sn, cs;
-                        sincospif(2.f * (float)x, &sn, &cs);
-                        const float2 d = sD[kk];                      // one address per wave: a broadcast
-                        J = fmaf(d.x, cs, J);
-                        J = fmaf(-d.y, sn, J);
-                    }
-                    sJ[tid] = J;
-                    jlast = J;
+                    jlast = drift_curve_point(sD, tid, ngrid, p.cfg.max_ppm, S);
+                    sJ[tid] = jlast;
                 }
                 __syncthreads();
-                // the first maximiser, every wave for itself: each lane over its own candidates in
-                // rising order, then across lanes
-                float bv = 0.f;
-                int best = 256;
-                bool any = false;
-                for (int g = lane; g < ngrid; g += 64) {
-                    const float v = sJ[g];
-                    any |= v != 0.f;
-                    if (best == 256 || v > bv) {
-                        bv = v;
-                        best = g;
-                    }
-                }
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) {
-                    const float ov = __shfl_xor(bv, o);
-                    const int oi = __shfl_xor(best, o);
-                    const bool take = oi < 256 && (best == 256 || ov > bv || (ov == bv && oi < best));
-                    bv = take ? ov : bv;
-                    best = take ? oi : best;
-                }
-                any = __any(any);
-                const int G = (ngrid - 1) / 2;
-                float off = 0.f;
-                if (best > 0 && best < ngrid - 1) {
-                    const float y0 = sJ[best - 1], y1 = sJ[best], y2 = sJ[best + 1];
-                    const float den = (y0 - y1) + (y2 - y1);
-                    if (den < 0.f) {
-                        off = 0.5f * (y0 - y2) / den;
-                        off = off < -0.5f ? -0.5f : (off > 0.5f ? 0.5f : off);
-                    }
-                }
-                const float step = p.cfg.max_ppm / (float)G;
-                const float r = any ? ((float)(best - G) + off) * step : 0.f;
+                const float r = drift_peak(sJ, ngrid, p.cfg.max_ppm, lane);   // every wave for itself
                 ppm = drift_track_clamp_ppm(__fadd_rn(ppm, __fmul_rn(p.cfg.gain, r)));   // acts from the next hop on
                 ++updates;
                 D = pf2{0.f, 0.f};

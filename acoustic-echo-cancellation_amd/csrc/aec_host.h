@@ -359,19 +359,25 @@ inline Check check_delay_track_open(int32_t B, int32_t max_lag, int32_t period, 
     return {};
 }
 
-// aec_delay_track_push's packet: `open` says whether the handle has a tracker.  The shape rules are
+// A tracker's packet (aec_delay_track_push, aec_drift_track_push): `open` says whether the handle
+// has that tracker, `open_first` and `in_place` are the two texts that name it.  The shape rules are
 // aec_stream_push's (every row holds max_hops hops; the counts are device data the kernel clamps);
-// the aligned hops cannot be written over the reference they are copied from.  The kernel addresses
-// a row through 32-bit byte offsets, hence the limit on max_hops (9 hours at 16 kHz in one packet).
-inline Check check_delay_track(bool open, const void* mic, const void* ref, const void* ref_out, int32_t max_hops,
-                               int64_t ld_in, int64_t ld_out) {
-    if (!open) return {AEC_ERR_INVALID_ARG, "aec_delay_track_open first"};
+// the hops written cannot go over the reference they are formed from.  The kernels address a row
+// through 32-bit byte offsets, hence the limit on max_hops (9 hours at 16 kHz in one packet).
+inline Check check_track_push(bool open, const char* open_first, const char* in_place, const void* mic, const void* ref,
+                              const void* ref_out, int32_t max_hops, int64_t ld_in, int64_t ld_out) {
+    if (!open) return {AEC_ERR_INVALID_ARG, open_first};
     if (!mic || !ref || !ref_out) return {AEC_ERR_INVALID_ARG, "null mic / ref / ref_out"};
     const Check c = check_stream_push(max_hops, ld_in, ld_out);
     if (c.status != AEC_OK) return c;
     if ((int64_t)256 * max_hops > kDelayMaxLen) return {AEC_ERR_UNSUPPORTED, "packet longer than 2^29 - 4096 samples"};
-    if (ref_out == ref) return {AEC_ERR_INVALID_ARG, "ref_out must not be ref (the alignment cannot run in place)"};
+    if (ref_out == ref) return {AEC_ERR_INVALID_ARG, in_place};
     return {};
+}
+inline Check check_delay_track(bool open, const void* mic, const void* ref, const void* ref_out, int32_t max_hops,
+                               int64_t ld_in, int64_t ld_out) {
+    return check_track_push(open, "aec_delay_track_open first", "ref_out must not be ref (the alignment cannot run in place)",
+                            mic, ref, ref_out, max_hops, ld_in, ld_out);
 }
 
 // The streaming drift tracker (aec_drift_track_*; kernel, state layout and the parameter ranges in
@@ -382,18 +388,11 @@ inline Check check_drift_track_open(int32_t B, const DriftTrackCfg& cfg) {
     return {};
 }
 
-// aec_drift_track_push's packet: aec_delay_track_push's rules (`open` says whether the handle has a
-// drift tracker; every row holds max_hops hops; the resampled hops cannot be written over the
-// reference they are formed from; 32-bit byte offsets into a row)
+// aec_drift_track_push's packet: check_track_push with the drift tracker's texts
 inline Check check_drift_track_args(bool open, const void* mic, const void* ref, const void* ref_out, int32_t max_hops,
                                     int64_t ld_in, int64_t ld_out) {
-    if (!open) return {AEC_ERR_INVALID_ARG, "aec_drift_track_open first"};
-    if (!mic || !ref || !ref_out) return {AEC_ERR_INVALID_ARG, "null mic / ref / ref_out"};
-    const Check c = check_stream_push(max_hops, ld_in, ld_out);
-    if (c.status != AEC_OK) return c;
-    if ((int64_t)256 * max_hops > kDelayMaxLen) return {AEC_ERR_UNSUPPORTED, "packet longer than 2^29 - 4096 samples"};
-    if (ref_out == ref) return {AEC_ERR_INVALID_ARG, "ref_out must not be ref (the resampler cannot run in place)"};
-    return {};
+    return check_track_push(open, "aec_drift_track_open first", "ref_out must not be ref (the resampler cannot run in place)",
+                            mic, ref, ref_out, max_hops, ld_in, ld_out);
 }
 
 // dst[B][4] = (mic, ref, near, 0) lengths as the kernels read them (normaliser
