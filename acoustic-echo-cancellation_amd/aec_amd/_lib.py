@@ -28,6 +28,7 @@ EXPORTS = ('aec_weights_count', 'aec_create', 'aec_set_weights', 'aec_set_erb', 
            'aec_process_siglens',
            'aec_prepare', 'aec_prepare_siglens', 'aec_process_prepared',
            'aec_stream_open', 'aec_stream_reset', 'aec_stream_step', 'aec_stream_push',
+           'aec_stream_open_rescue', 'aec_stream_rescue_counts',
            'aec_delay_estimate', 'aec_delay_apply', 'aec_drift_estimate', 'aec_drift_apply',
            'aec_delay_track_open', 'aec_delay_track_reset', 'aec_delay_track_push',
            'aec_drift_track_open', 'aec_drift_track_reset', 'aec_drift_track_push',
@@ -127,6 +128,11 @@ def load():
     lib.aec_stream_step.restype = ctypes.c_int
     lib.aec_stream_push.argtypes = [P, P, P, ctypes.c_int64, P, ctypes.c_int64, P, ctypes.c_int32, P]
     lib.aec_stream_push.restype = ctypes.c_int
+    if LIB_PATH == _DEFAULT_LIB or hasattr(lib, 'aec_stream_open_rescue'):   # absent from an older A/B build
+        lib.aec_stream_open_rescue.argtypes = [P, ctypes.c_int32]
+        lib.aec_stream_open_rescue.restype = ctypes.c_int
+        lib.aec_stream_rescue_counts.argtypes = [P, P, P]
+        lib.aec_stream_rescue_counts.restype = ctypes.c_int
     if LIB_PATH == _DEFAULT_LIB or hasattr(lib, 'aec_delay_estimate'):   # absent from an older A/B build
         lib.aec_delay_estimate.argtypes = [P, P, P, P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, P, P, P]
         lib.aec_delay_estimate.restype = ctypes.c_int
@@ -276,6 +282,7 @@ class Handle:
         check(st, None, 'aec_create')
         self.h = h
         self.device = device
+        self.rescue = False                # the Kalman canceller's rescue is on (set_canceller_rescue)
 
     def set_weights(self, blob):
         import numpy as np
@@ -293,11 +300,13 @@ class Handle:
         """kind: 'nlms' / 0 or 'kalman' / 1 (aec_set_canceller)."""
         kind = {'nlms': 0, 'kalman': 1}.get(kind, kind)
         check(self.lib.aec_set_canceller(self.h, int(kind), float(a), float(p0)), self.h, 'aec_set_canceller')
+        self.rescue = False                # every successful aec_set_canceller switches the rescue off
 
     def set_canceller_rescue(self, on, mu=0.3, gamma=0.9, ratio=0.5):
         """The Kalman canceller's rescue from echo-path changes (aec_set_canceller_rescue)."""
         check(self.lib.aec_set_canceller_rescue(self.h, int(bool(on)), float(mu), float(gamma), float(ratio)), self.h,
               'aec_set_canceller_rescue')
+        self.rescue = bool(on)
 
     def set_debug(self, on: bool):
         check(self.lib.aec_set_debug(self.h, int(bool(on))), self.h, 'aec_set_debug')
@@ -333,6 +342,14 @@ class Handle:
 
     def stream_open(self, B):
         check(self.lib.aec_stream_open(self.h, int(B)), self.h, 'aec_stream_open')
+
+    def stream_open_rescue(self, B):
+        """Streams of a handle with the canceller rescue on (aec_stream_open_rescue)."""
+        check(self.lib.aec_stream_open_rescue(self.h, int(B)), self.h, 'aec_stream_open_rescue')
+
+    def stream_rescue_counts(self, counts_ptr, stream):
+        """counts_ptr: device [B] int64, the copies of every stream since open / reset"""
+        check(self.lib.aec_stream_rescue_counts(self.h, counts_ptr, stream), self.h, 'aec_stream_rescue_counts')
 
     def stream_reset(self, b, stream):
         check(self.lib.aec_stream_reset(self.h, int(b), stream), self.h, 'aec_stream_reset')

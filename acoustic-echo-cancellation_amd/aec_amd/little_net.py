@@ -338,7 +338,10 @@ class Little_net(nn.Module):
     # --- streaming (include/aec_hip.h aec_stream_*) ------------------------------
     def stream_open(self, B, erb, device=None):
         """Open B concurrent streams (state zeroed) on ``device``: afterwards
-        ``stream_step`` advances every stream by one 256-sample hop."""
+        ``stream_step`` advances every stream by one 256-sample hop.  With the
+        Kalman canceller's rescue on (``nlms['rescue']``) the streams carry the
+        shadow filter (aec_stream_open_rescue) and count its copies
+        (``stream_rescue_counts``)."""
         if torch.is_grad_enabled() and self.training:
             raise NotImplementedError('streaming is inference-only: use net.eval() and torch.no_grad()')
         device = torch.device(device or 'cuda')
@@ -348,8 +351,12 @@ class Little_net(nn.Module):
             raise ValueError(f'erb must be [257, 32], got {tuple(erb.shape)}')
         h, idx = self._handle(device)
         self._sync_erb(h, idx, erb)
-        h.stream_open(B)
+        if h.rescue:
+            h.stream_open_rescue(B)
+        else:
+            h.stream_open(B)
         self._stream = (h, torch.device('cuda', idx), int(B))
+        self._stream_rescue = bool(h.rescue)
 
     def _stream_state(self):
         st = getattr(self, '_stream', None)
@@ -361,6 +368,19 @@ class Little_net(nn.Module):
         """Zero stream b's state (b = -1: every stream) for a new utterance."""
         h, device, _ = self._stream_state()
         h.stream_reset(b, torch.cuda.current_stream(device).cuda_stream)
+
+    def stream_rescue_counts(self):
+        """Per stream, the (bin, frame) copies of the canceller rescue's shadow since
+        ``stream_open`` / ``stream_reset``: int64 [B] on the streams' device, written
+        in stream order (nothing synchronises).  A count that moves says that
+        stream's echo path changed."""
+        h, device, B = self._stream_state()
+        if not getattr(self, '_stream_rescue', False):
+            raise RuntimeError("the open streams have no canceller rescue (nlms['rescue'])")
+        counts = torch.empty(B, device=device, dtype=torch.int64)
+        with torch.cuda.device(device):
+            h.stream_rescue_counts(counts.data_ptr(), torch.cuda.current_stream(device).cuda_stream)
+        return counts
 
     def stream_step(self, mic, ref):
         """mic, ref [B, 256] float32 (hop k of every stream, already normalised

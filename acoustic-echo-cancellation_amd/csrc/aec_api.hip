@@ -124,6 +124,7 @@ struct aec_handle {
     float* d_state = nullptr;
     int32_t stream_B = 0;
     int64_t stream_stride = 0;
+    bool stream_rescue = false;  // the state is a rescue stream's (aec_stream_open_rescue): shadow rows, copy counter
     // streaming delay tracker (aec_delay_track_*): per-stream state [track_B][track_stride]
     float* d_track = nullptr;
     float* d_drift_tab = nullptr;   // the resampler's interpolation table (aec_drift.h build_drift_table)
@@ -279,6 +280,7 @@ const char* aec_last_error(const aec_handle* h) { return h ? h->err.c_str() : "n
 const char* aec_build_info(void) {
     static const std::string info = std::string("arch=gfx950 ab_knobs=") + (AEC_AB_BUILD ? "on" : "off") +
                                     " canceller_rescue=kalman:1-" + std::to_string(aec::kRescueMaxTaps) +
+                                    " stream_rescue=kalman:1-" + std::to_string(aec::kRescueMaxTaps) +
                                     " mode_knobs=" + aec::kModeKnobs;
     return info.c_str();
 }
@@ -848,21 +850,46 @@ aec_status aec_erb_tables_check(const float* erb, const float* mags, const float
     return AEC_OK;
 }
 
-aec_status aec_stream_open(aec_handle* h, int32_t B) {
-    if (!h) return AEC_ERR_INVALID_ARG;
-    if (B < 1) return fail(h, AEC_ERR_INVALID_ARG, "stream count must be >= 1");
-    if (h->rescue.on) return fail(h, AEC_ERR_UNSUPPORTED, "the streaming kernels have no canceller rescue (aec_set_canceller_rescue)");
-    AEC_ON_DEVICE(h);
-    const int64_t stride = stream_state_floats(h->cfg.nlms_taps, h->canc.kind);
+// B streams' state for the handle's canceller (rescue: with the shadow's rows, which like the
+// counter start at zero): zeroed, the Kalman covariances at p0, a previous state replaced
+static aec_status stream_open_state(aec_handle* h, int32_t B, bool rescue) {
+    const int64_t stride = stream_state_floats(h->cfg.nlms_taps, h->canc.kind, rescue);
+    h->stream_rescue = false;
     const aec_status s = state_open(h, h->d_state, h->stream_B, B, stride);
     if (s != AEC_OK) return s;
     h->stream_stride = stride;
+    h->stream_rescue = rescue;
     if (h->canc.kind == kCancellerKalman) {
         h->stream_B = 0;                  // no stream to step until the covariances are in place
         HIP_TRY(h, launch_stream_cov_fill(h->d_state, stride, 0, B, h->cfg.nlms_taps, h->canc.p0, nullptr));
         HIP_TRY(h, hipStreamSynchronize(nullptr));
         h->stream_B = B;
     }
+    return AEC_OK;
+}
+
+aec_status aec_stream_open(aec_handle* h, int32_t B) {
+    if (!h) return AEC_ERR_INVALID_ARG;
+    if (B < 1) return fail(h, AEC_ERR_INVALID_ARG, "stream count must be >= 1");
+    if (h->rescue.on) return fail(h, AEC_ERR_UNSUPPORTED, "this state has no rows for the canceller rescue's shadow filter: aec_stream_open_rescue opens a rescue handle's streams");
+    AEC_ON_DEVICE(h);
+    return stream_open_state(h, B, false);
+}
+
+aec_status aec_stream_open_rescue(aec_handle* h, int32_t B) {
+    if (!h) return AEC_ERR_INVALID_ARG;
+    if (!h->rescue.on) return fail(h, AEC_ERR_INVALID_ARG, "the canceller rescue is not on for this handle (aec_set_canceller_rescue)");
+    if (B < 1) return fail(h, AEC_ERR_INVALID_ARG, "stream count must be >= 1");
+    AEC_ON_DEVICE(h);
+    return stream_open_state(h, B, true);
+}
+
+aec_status aec_stream_rescue_counts(aec_handle* h, int64_t* counts, void* stream) {
+    if (!h) return AEC_ERR_INVALID_ARG;
+    if (!h->d_state || !h->stream_rescue) return fail(h, AEC_ERR_INVALID_ARG, "aec_stream_open_rescue first");
+    if (!counts) return fail(h, AEC_ERR_INVALID_ARG, "null counts");
+    AEC_ON_DEVICE(h);
+    HIP_TRY(h, launch_stream_rescue_counts(h->d_state, h->stream_stride, h->stream_B, counts, reinterpret_cast<hipStream_t>(stream)));
     return AEC_OK;
 }
 
@@ -890,6 +917,10 @@ aec_status aec_stream_step(aec_handle* h, const float* mic, const float* ref, in
     a.w = h->d_w; a.tables = reinterpret_cast<const float*>(h->d_tab);
     a.sched = h->d_sched; a.sched_len = h->sched_len; a.bintab = h->d_bintab;
     a.c = h->canceller();
+    if (h->stream_rescue) {
+        HIP_TRY(h, launch_stream_step_rescue(a, h->rescue, h->stream_B, reinterpret_cast<hipStream_t>(stream)));
+        return AEC_OK;
+    }
     HIP_TRY(h, launch_stream_step(a, h->stream_B, reinterpret_cast<hipStream_t>(stream)));
     return AEC_OK;
 }
@@ -912,7 +943,12 @@ aec_status aec_stream_push(aec_handle* h, const float* mic, const float* ref, in
     a.hops = hops; a.max_hops = max_hops;
     // one hop for every stream is the step: the same result from the kernel without the hop loop
     if (!hops && max_hops == 1) {
-        HIP_TRY(h, launch_stream_step(a.s, h->stream_B, reinterpret_cast<hipStream_t>(stream)));
+        if (h->stream_rescue) HIP_TRY(h, launch_stream_step_rescue(a.s, h->rescue, h->stream_B, reinterpret_cast<hipStream_t>(stream)));
+        else HIP_TRY(h, launch_stream_step(a.s, h->stream_B, reinterpret_cast<hipStream_t>(stream)));
+        return AEC_OK;
+    }
+    if (h->stream_rescue) {
+        HIP_TRY(h, launch_stream_push_rescue(a, h->rescue, h->stream_B, reinterpret_cast<hipStream_t>(stream)));
         return AEC_OK;
     }
     HIP_TRY(h, launch_stream_push(a, h->stream_B, reinterpret_cast<hipStream_t>(stream)));

@@ -98,7 +98,10 @@ inline std::string check_canceller_rescue(int taps, int kind, int on, float mu, 
 // One stream's canceller state between streaming calls: rows of kCancellerRow float2 (bin slot k;
 // slot 0 the real pair of bins 0 and 256): W[0 .. taps), the raw far-end history
 // R[t-1 .. t-taps+1], the NLMS power row (unused by the Kalman canceller), then for the Kalman
-// canceller the taps covariance rows P[0 .. taps) and one row psi.  -1: the kind has no such row.
+// canceller the taps covariance rows P[0 .. taps) and one row psi.  A rescue stream
+// (aec_stream_open_rescue) keeps the Kalman rows where they are and appends the
+// shadow's: Ws[0 .. taps), Pn, qe, qs (RescueBin's ws, pn, qe, qs; taps + 3 rows, zero at stream
+// start).  The shadow has no history of its own.  -1: the state has no such row.
 constexpr int kCancellerRow = 256;
 struct CancellerRows {
     int w = 0;          // first of `taps` rows
@@ -108,10 +111,15 @@ struct CancellerRows {
     int cov = -1;       // Kalman: first of `taps` rows
     int psi = -1;       // Kalman
     int rows = 0;       // rows per stream
+    int ws = -1;        // rescue: first of `taps` rows
+    int pn = -1;        // rescue
+    int qe = -1;        // rescue
+    int qs = -1;        // rescue
     constexpr int64_t floats() const { return (int64_t)rows * kCancellerRow * 2; }
     constexpr size_t bytes() const { return (size_t)rows * kCancellerRow * 2 * sizeof(float); }
 };
-constexpr CancellerRows canceller_rows(int taps, bool kalman) {
+// rescue: the Kalman canceller's shadow rows follow (ignored for the NLMS, which has no rescue)
+constexpr CancellerRows canceller_rows(int taps, bool kalman, bool rescue = false) {
     CancellerRows r;
     if (taps <= 0) return r;
     r.hist = taps;
@@ -122,6 +130,13 @@ constexpr CancellerRows canceller_rows(int taps, bool kalman) {
         r.cov = r.rows;
         r.psi = r.cov + taps;
         r.rows = r.psi + 1;
+        if (rescue) {
+            r.ws = r.rows;
+            r.pn = r.ws + taps;
+            r.qe = r.pn + 1;
+            r.qs = r.qe + 1;
+            r.rows = r.qs + 1;
+        }
     }
     return r;
 }

@@ -26,13 +26,23 @@ constexpr int kK2nMaxTaps = 8;      // most taps K2n (and the per-lane recursion
 constexpr int kMaxTaps = 16;        // most taps of the linear stage (256 ms of far-end history)
 
 inline int64_t num_frames(int64_t n) { return n / 256 + 1; }
-// Floats of one stream's state (aec_stream_*; layout in aec_launch.h): kStreamStatePrefix, then
-// the canceller's rows (aec_canceller.h canceller_rows).  (0 taps with the Kalman kind, which
-// aec_set_canceller refuses, keeps the one row this function has always counted for it.)
+// Floats of one stream's state (aec_stream_*): kStreamStatePrefix, then the canceller's rows
+// (aec_canceller.h canceller_rows; rescue: with the shadow's rows, aec_stream_open_rescue).
+// (0 taps with the Kalman kind, which aec_set_canceller refuses, keeps the one row this function
+// has always counted for it.)  The prefix, floats:
+//   [0, 512)     previous input hop: mic (256), ref (256)
+//   [512, 768)   OLA tail: second half of the previous synthesis frame
+//   [768, 800)   GRU h
+//   [800]        a rescue stream's copy counter (uint32: (bin, frame) copies since open / reset)
+//   (801, 1024)  unused
 constexpr int kStreamStatePrefix = 1024;
-inline int64_t stream_state_floats(int taps, int kalman = 0) {
+constexpr int kStPrev = 0;
+constexpr int kStTail = 512;
+constexpr int kStH = 768;
+constexpr int kStCopies = 800;
+inline int64_t stream_state_floats(int taps, int kalman = 0, int rescue = 0) {
     if (taps <= 0) return kStreamStatePrefix + (kalman ? 2 * kCancellerRow : 0);
-    return kStreamStatePrefix + canceller_rows(taps, kalman != 0).floats();
+    return kStreamStatePrefix + canceller_rows(taps, kalman != 0, rescue != 0).floats();
 }
 inline int64_t out_len(int64_t n) { return 256 * (n / 256); }
 

@@ -95,14 +95,10 @@ struct SynthArgs {
 };
 
 // Fused streaming step (aec_stream.hip): one 256-sample hop of B streams.
-// Per-stream state, floats (stride = stream_state_floats(taps, kalman), aec_host.h):
-//   [0, 512)     previous input hop: mic (256), ref (256)
-//   [512, 768)   OLA tail: second half of the previous synthesis frame
-//   [768, 800)   GRU h
-//   [1024, ...)  canceller: canceller_rows(taps, kalman) (aec_canceller.h)
-constexpr int kStPrev = 0;
-constexpr int kStTail = 512;
-constexpr int kStH = 768;
+// Per-stream state, floats (stride = stream_state_floats(taps, kalman, rescue); the prefix's layout
+// and kStPrev / kStTail / kStH / kStCopies: aec_host.h):
+//   [0, 1024)    the prefix: previous input hop, OLA tail, GRU h, a rescue stream's copy counter
+//   [1024, ...)  canceller: canceller_rows(taps, kalman, rescue) (aec_canceller.h)
 constexpr int kStNlms = kStreamStatePrefix;
 
 struct StreamStepArgs {
@@ -129,6 +125,21 @@ struct StreamPushArgs {
     const int32_t* hops;     // device [B] hop counts, clamped to [0, max_hops] by the kernel; null: max_hops each
     int32_t max_hops;
 };
+
+// The argument blocks of the rescue instantiations (aec_stream_rescue.hip): the plain blocks with
+// the rescue's parameters behind them, so the other instantiations' blocks stay as they are
+struct StreamStepRescueArgs : StreamStepArgs {
+    CancellerRescue r;
+};
+struct StreamPushRescueArgs : StreamPushArgs {
+    CancellerRescue r;
+};
+static_assert(std::is_trivially_copyable<StreamStepRescueArgs>::value && std::is_trivially_copyable<StreamPushRescueArgs>::value,
+              "kernel argument blocks");
+template <bool RESCUE>
+using StreamStepArgsT = std::conditional_t<RESCUE, StreamStepRescueArgs, StreamStepArgs>;
+template <bool RESCUE>
+using StreamPushArgsT = std::conditional_t<RESCUE, StreamPushRescueArgs, StreamPushArgs>;
 
 // dynamic LDS bytes (must match the carve in the kernels)
 inline size_t analysis_smem_bytes(int sched_len) {
@@ -187,6 +198,12 @@ hipError_t launch_stream_cov_fill(float* state, int64_t stride, int first, int c
 // 9..16 taps (aec_stream_long.hip): the same kernel templates; launch_stream_step / _push forward here
 hipError_t launch_stream_step_long(const StreamStepArgs& a, int B, hipStream_t st);
 hipError_t launch_stream_push_long(const StreamPushArgs& a, int B, hipStream_t st);
+// The Kalman canceller with its rescue, 1..8 taps (aec_stream_rescue.hip): the same templates over a
+// state with the shadow's rows (canceller_rows(taps, true, true)).  launch_stream_rescue_counts:
+// counts[b] = stream b's copy counter (kStCopies), B streams
+hipError_t launch_stream_step_rescue(const StreamStepArgs& a, const CancellerRescue& r, int B, hipStream_t st);
+hipError_t launch_stream_push_rescue(const StreamPushArgs& a, const CancellerRescue& r, int B, hipStream_t st);
+hipError_t launch_stream_rescue_counts(const float* state, int64_t stride, int B, int64_t* counts, hipStream_t st);
 // K3+K4 fused (aec_gru_synth.hip): GRU + head + synthesis of the NLMS error spectrum, one stream per
 // block or two (Plan::gru_one, aec_host.h)
 hipError_t launch_gru_synth(const GruArgs& g, const SynthArgs& y, int B, bool one_per_block, hipStream_t st);

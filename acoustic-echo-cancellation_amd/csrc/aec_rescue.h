@@ -102,4 +102,45 @@ struct RescueBin {
     }
 };
 
+// Bin slot k of a rescue stream's saved state (nst: the stream's rows, canceller_rows(taps, true,
+// true)) into the bin and back: the main filter through bin_load / bin_store (aec_frame.h), whose
+// rows lie where a plain Kalman stream has them, then the shadow's rows.  The streaming kernels
+// that load the main filter themselves call the shadow halves alone.
+template <int TAPS>
+__device__ __forceinline__ void shadow_load(RescueBin<TAPS>& rb, const float2* nst, int k) {
+    constexpr CancellerRows R = canceller_rows(TAPS, true, true);
+#pragma unroll
+    for (int l = 0; l < TAPS; ++l) rb.ws[l] = nst[(R.ws + l) * kCancellerRow + k];
+    rb.pn = nst[R.pn * kCancellerRow + k];
+    rb.qe = nst[R.qe * kCancellerRow + k];
+    rb.qs = nst[R.qs * kCancellerRow + k];
+}
+template <int TAPS>
+__device__ __forceinline__ void shadow_store(const RescueBin<TAPS>& rb, float2* nst, int k) {
+    constexpr CancellerRows R = canceller_rows(TAPS, true, true);
+#pragma unroll
+    for (int l = 0; l < TAPS; ++l) nst[(R.ws + l) * kCancellerRow + k] = rb.ws[l];
+    nst[R.pn * kCancellerRow + k] = rb.pn;
+    nst[R.qe * kCancellerRow + k] = rb.qe;
+    nst[R.qs * kCancellerRow + k] = rb.qs;
+}
+template <int TAPS>
+__device__ __forceinline__ void bin_load(RescueBin<TAPS>& rb, const float2* nst, int k, float p0) {
+    bin_load(rb.k, nst, k, p0);
+    shadow_load(rb, nst, k);
+}
+template <int TAPS>
+__device__ __forceinline__ void bin_store(const RescueBin<TAPS>& rb, float2* nst, int k) {
+    bin_store(rb.k, nst, k);
+    shadow_store(rb, nst, k);
+}
+
+// This wave's copies of one frame, for a rescue stream's counter: the bins whose x half copied (a
+// complex lane decides the same in both halves), and on the slot-0 lane, which runs the real bins
+// 0 and 256, bin 256's own decision.  One ballot and one popcount; the result is wave-uniform
+// except on the slot-0 lane, and only a wave's first lane's value is added to the state.
+__device__ __forceinline__ uint32_t rescue_copies(bool dual, bool cx, bool cy) {
+    return (uint32_t)__popcll(__ballot(cx)) + ((dual && cy) ? 1u : 0u);
+}
+
 }  // namespace aec

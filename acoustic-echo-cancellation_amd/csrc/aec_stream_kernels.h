@@ -1,6 +1,7 @@
 // aec_stream_kernels.h — the fused streaming kernels (stream_step_kernel, stream_push_kernel) as
 // templates over the tap count and the canceller.  aec_stream.hip instantiates them for 0..8 taps
-// and aec_stream_long.hip for 9..16 (a translation unit of its own: the two compile side by side).
+// and aec_stream_long.hip for 9..16 (a translation unit of its own: the two compile side by side);
+// aec_stream_rescue.hip, a third, the Kalman canceller with its rescue for 1..8 taps.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -8,6 +9,7 @@
 #include "aec_fft.h"
 #include "aec_frame.h"
 #include "aec_launch.h"
+#include "aec_rescue.h"
 #include "aec_stft.h"
 #include "aec_tables.h"
 
@@ -16,9 +18,21 @@ namespace aec {
 constexpr int kStreamThreads = 256;
 constexpr int kSchedMax = 48;                 // ErbTables: L <= 48
 
-// KALMAN: the canceller is KalmanBin, else NlmsBin (CancellerBin); state rows: canceller_rows
-template <int TAPS, bool KALMAN = false>
-__global__ __launch_bounds__(kStreamThreads) void stream_step_kernel(StreamStepArgs p) {
+// The bin a stream steps: CancellerBin, or with the rescue RescueBin, whose main filter (the
+// CancellerBin the kernels load, store and, without the rescue, step) is its member k
+template <int TAPS, bool KALMAN, bool RESCUE>
+using StreamBin = std::conditional_t<RESCUE, RescueBin<(TAPS > 0 ? TAPS : 1)>, CancellerBin<TAPS, KALMAN>>;
+template <int TAPS>
+__device__ __forceinline__ KalmanBin<TAPS>& main_bin(RescueBin<TAPS>& b) { return b.k; }
+template <class BIN>
+__device__ __forceinline__ BIN& main_bin(BIN& b) { return b; }
+
+// KALMAN: the canceller is KalmanBin, else NlmsBin (CancellerBin); state rows: canceller_rows.
+// RESCUE (Kalman, 1..8 taps): the bin is RescueBin, the state carries the shadow's rows behind the
+// Kalman canceller's and the prefix counts the copies (kStCopies); p.r holds the rescue's values
+template <int TAPS, bool KALMAN = false, bool RESCUE = false>
+__global__ __launch_bounds__(kStreamThreads) void stream_step_kernel(StreamStepArgsT<RESCUE> p) {
+    static_assert(!RESCUE || (KALMAN && TAPS >= 1 && TAPS <= kRescueMaxTaps), "the rescue: Kalman, 1..8 taps");
     __shared__ __attribute__((aligned(16))) float4 sSched[kSchedMax * 16];
     __shared__ int2 sComb[32];
     __shared__ __attribute__((aligned(16))) float2 sTw512[258];
@@ -89,7 +103,8 @@ __global__ __launch_bounds__(kStreamThreads) void stream_step_kernel(StreamStepA
     // NLMS bin slot k = tid (slot 0: the real pair (0, 256)); taps, power and
     // the raw far-end history r[t-1 .. t-TAPS+1] from the state
     constexpr CancellerRows R = canceller_rows(TAPS, KALMAN);
-    CancellerBin<TAPS, KALMAN> nb;
+    StreamBin<TAPS, KALMAN, RESCUE> sb;
+    CancellerBin<TAPS, KALMAN>& nb = main_bin(sb);
     float2 rh[TAPS > 1 ? TAPS - 1 : 1];
     float2* nst = reinterpret_cast<float2*>(st + kStNlms);
     if constexpr (TAPS > 0) {
@@ -118,6 +133,7 @@ __global__ __launch_bounds__(kStreamThreads) void stream_step_kernel(StreamStepA
             const float2 pp = nst[R.power * 256 + tid];
             nb.p = pp;
         }
+        if constexpr (RESCUE) shadow_load(sb, nst, tid);
     }
 
     // role weights: wave 0 the recurrence (W_hh k-halves, as gru_kernel's
@@ -171,7 +187,17 @@ __global__ __launch_bounds__(kStreamThreads) void stream_step_kernel(StreamStepA
 
     // ---- P2: NLMS step of every bin (E row) ----
     if constexpr (TAPS > 0) {
-        const float2 e = nb.step(sRow[0][tid], sRow[1][tid], p.c.gain, p.c.beta, p.c.delta);
+        float2 e;
+        if constexpr (RESCUE) {
+            // the main filter's step, the shadow's and the copy (RescueBin::step, as aec_rescue.hip calls it)
+            bool cx, cy;
+            e = sb.step(sRow[0][tid], sRow[1][tid], p.c.gain, p.c.beta, p.c.delta, p.c.p0, p.r.mu, p.r.gamma, p.r.ratio, cx, cy);
+            const uint32_t copies = rescue_copies(tid == 0, cx, cy);
+            if (lane == 0) atomicAdd(reinterpret_cast<uint32_t*>(st + kStCopies), copies);
+            shadow_store(sb, nst, tid);
+        } else {
+            e = nb.step(sRow[0][tid], sRow[1][tid], p.c.gain, p.c.beta, p.c.delta);
+        }
         sRow[2][tid] = e;
 #pragma unroll
         for (int l = 0; l < TAPS; ++l) nst[(R.w + l) * 256 + tid] = nb.w[l];
@@ -258,8 +284,11 @@ __global__ __launch_bounds__(kStreamThreads) void stream_step_kernel(StreamStepA
 // next hop's P1 (wave 0 writes sScr, sRow, sMicErb, sRefErb and reads sStg) behind every thread's P8
 // (reads sScr[0], writes sStg).  sH needs none of its own: hop j reads row j & 1 and writes the
 // other, whose last reader (P5 of hop j-1, on the same wave) is several barriers back.
-template <int TAPS, bool KALMAN = false>
-__global__ __launch_bounds__(kStreamThreads) void stream_push_kernel(StreamPushArgs q) {
+// RESCUE: as in the step; the shadow's rows are read once per packet and written once, after the
+// last hop, and the packet's copies, counted in a register, are added to the state once.
+template <int TAPS, bool KALMAN = false, bool RESCUE = false>
+__global__ __launch_bounds__(kStreamThreads) void stream_push_kernel(StreamPushArgsT<RESCUE> q) {
+    static_assert(!RESCUE || (KALMAN && TAPS >= 1 && TAPS <= kRescueMaxTaps), "the rescue: Kalman, 1..8 taps");
     __shared__ __attribute__((aligned(16))) float4 sSched[kSchedMax * 16];
     __shared__ int2 sComb[32];
     __shared__ __attribute__((aligned(16))) float2 sTw512[258];
@@ -331,9 +360,10 @@ __global__ __launch_bounds__(kStreamThreads) void stream_push_kernel(StreamPushA
     float tail = st[kStTail + tid];
 
     // canceller bin slot k = tid (slot 0: the real pair (0, 256)), as the step loads it
-    CancellerBin<TAPS, KALMAN> nb;
+    StreamBin<TAPS, KALMAN, RESCUE> nb;
     float2* nst = reinterpret_cast<float2*>(st + kStNlms);
     if constexpr (TAPS > 0) bin_load(nb, nst, tid, p.c.p0);
+    [[maybe_unused]] uint32_t copies = 0;     // RESCUE: this wave's copies over the packet's hops
 
     // role weights: the step's three sets (wave 0: W_hh k-halves; threads 64..159: a W_ih row; wave 3:
     // the head's rows) in ONE register array, since a thread has one role and the sets stay live
@@ -396,7 +426,14 @@ __global__ __launch_bounds__(kStreamThreads) void stream_push_kernel(StreamPushA
 
         // ---- P2: canceller step of every bin (E row); the state stays in registers ----
         if constexpr (TAPS > 0) {
-            sRow[2][tid] = nb.step(sRow[0][tid], sRow[1][tid], p.c.gain, p.c.beta, p.c.delta);
+            if constexpr (RESCUE) {
+                bool cx, cy;
+                sRow[2][tid] = nb.step(sRow[0][tid], sRow[1][tid], p.c.gain, p.c.beta, p.c.delta, p.c.p0, q.r.mu, q.r.gamma,
+                                       q.r.ratio, cx, cy);
+                copies += rescue_copies(tid == 0, cx, cy);
+            } else {
+                sRow[2][tid] = nb.step(sRow[0][tid], sRow[1][tid], p.c.gain, p.c.beta, p.c.delta);
+            }
             __syncthreads();
         }
 
@@ -476,9 +513,12 @@ __global__ __launch_bounds__(kStreamThreads) void stream_push_kernel(StreamPushA
     st[kStTail + tid] = tail;
     if (tid < 32) st[kStH + tid] = sH[n & 1][tid];
     if constexpr (TAPS > 0) bin_store(nb, nst, tid);
+    if constexpr (RESCUE) {
+        if (lane == 0) atomicAdd(reinterpret_cast<uint32_t*>(st + kStCopies), copies);
+    }
 }
 
-// The launches of one translation unit's tap range [LO, HI]
+// The launches of one translation unit's tap range [LO, HI] (without the rescue)
 template <int LO, int HI>
 hipError_t launch_stream_step_range(const StreamStepArgs& a, int B, hipStream_t s) {
     return dispatch_canceller<LO, HI>(a.c, hipErrorInvalidValue, [&](auto taps, auto kalman) {

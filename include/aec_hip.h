@@ -117,8 +117,10 @@ aec_status aec_set_canceller(aec_handle* h, int32_t kind, float a, float p0);
  * as does every later successful aec_set_canceller.
  * AEC_ERR_INVALID_ARG: the Kalman canceller is not selected, a streaming state is
  * open, or (on != 0) mu negative or not finite, gamma outside [0, 1), ratio
- * negative or not finite.  AEC_ERR_UNSUPPORTED: nlms_taps > 8.  aec_stream_open on
- * a handle with the rescue on returns AEC_ERR_UNSUPPORTED. */
+ * negative or not finite.  AEC_ERR_UNSUPPORTED: nlms_taps > 8.  Streaming: a
+ * rescue handle opens its streams with aec_stream_open_rescue (below), whose state
+ * carries the shadow; aec_stream_open on a handle with the rescue on returns
+ * AEC_ERR_UNSUPPORTED. */
 aec_status aec_set_canceller_rescue(aec_handle* h, int32_t on, float mu, float gamma, float ratio);
 
 aec_status aec_set_weights(aec_handle* h, const float* weights, size_t n_weights);
@@ -191,7 +193,9 @@ aec_status aec_process_prepared(aec_handle* h, uint64_t token, const float* mic,
  * past n) reproduces aec_process's out row for that stream.  The hops must
  * already be normalised: x - mean(x)/std(x) (ERB.py:254-256) needs the whole
  * utterance, which a stream does not have; near / loss are not computed.
- *   aec_stream_open(h, B)        B concurrent streams; state zeroed (Kalman: P = p0)
+ *   aec_stream_open(h, B)        B concurrent streams; state zeroed (Kalman: P = p0);
+ *        AEC_ERR_UNSUPPORTED on a handle with the canceller rescue on, whose
+ *        streams aec_stream_open_rescue opens
  *   aec_stream_reset(h, b, st)   stream b's state (-1: all streams) back to that start
  *   aec_stream_step(h, mic, ref, ld_in, out, ld_out, st)
  *        mic, ref: device [B, ld_in] float32, hop k of every stream;
@@ -226,6 +230,28 @@ aec_status aec_stream_step(aec_handle* h, const float* mic, const float* ref, in
  * ld_out below 256 max_hops. */
 aec_status aec_stream_push(aec_handle* h, const float* mic, const float* ref, int64_t ld_in,
                            float* out, int64_t ld_out, const int32_t* hops, int32_t max_hops, void* stream);
+
+/* Streams of a handle with the Kalman canceller's rescue on (aec_set_canceller_rescue;
+ * DESIGN.md 29): aec_stream_open for a state that also carries, per stream, the
+ * shadow filter (Ws, Pn, qe, qs: nlms_taps + 3 rows of 256 float2 behind the Kalman
+ * canceller's, all zero at stream start) and a counter of the copies.  Zeroed
+ * state, P = p0, a previous state of either kind replaced.  Afterwards
+ * aec_stream_reset, aec_stream_step and aec_stream_push work on that state as on
+ * any other, packets and per-stream counts included, and step and push mix; a
+ * hop runs the batch kernel's bin, so a streamed utterance reproduces the rescue
+ * handle's aec_process row bit for bit.  While the state is open aec_set_canceller
+ * and aec_set_canceller_rescue refuse, as for any open stream.
+ * AEC_ERR_INVALID_ARG: the rescue is not on for the handle, or B < 1.
+ *
+ * aec_stream_rescue_counts: counts (DEVICE [B] int64) receives, in stream order,
+ * the number of (bin, frame) copies of each stream since open / reset, bins 0 and
+ * 256 counted separately: what a serving loop watches to learn that an echo path
+ * changed.  A stream reset starts again at 0; a 0-hop packet leaves the count as
+ * it is.  The counter is 32 bits wide in the state (2^32 copies: 18 hours of
+ * every bin copying in every frame).  AEC_ERR_INVALID_ARG: no open rescue state,
+ * or counts null. */
+aec_status aec_stream_open_rescue(aec_handle* h, int32_t B);
+aec_status aec_stream_rescue_counts(aec_handle* h, int64_t* counts, void* stream);
 
 /* Far-end bulk delay (no reference counterpart).  The cancellers
  * see nlms_taps <= 16 frames (256 ms) of far-end history; play-out and capture
@@ -525,9 +551,11 @@ int64_t aec_out_len(int64_t n_samples);      /* 256*(n//256) */
 const char* aec_last_error(const aec_handle* h);
 
 /* Build description of this library (no reference counterpart: bench and test
- * provenance).  "arch=gfx950 ab_knobs=off mode_knobs=<names>": ab_knobs=on marks
+ * provenance).  "arch=gfx950 ab_knobs=off ... mode_knobs=<names>": ab_knobs=on marks
  * an A/B build (-DAEC_AB_KNOBS) that reads timing-only / work-skipping knobs;
- * mode_knobs lists the environment variables that select tested modes. */
+ * canceller_rescue= and stream_rescue= name the canceller and tap range the batch
+ * and the streaming rescue are built for; mode_knobs lists the environment
+ * variables that select tested modes. */
 const char* aec_build_info(void);
 void aec_destroy(aec_handle* h);
 
