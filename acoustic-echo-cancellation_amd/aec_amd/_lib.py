@@ -24,6 +24,7 @@ _STATUS = {0: 'AEC_OK', 1: 'AEC_ERR_INVALID_ARG', 2: 'AEC_ERR_OOM', 3: 'AEC_ERR_
 
 # every symbol include/aec_hip.h declares
 EXPORTS = ('aec_weights_count', 'aec_create', 'aec_set_weights', 'aec_set_erb', 'aec_set_canceller', 'aec_set_canceller_rescue',
+           'aec_set_canceller_stereo', 'aec_process_stereo',
            'aec_process',
            'aec_process_siglens',
            'aec_prepare', 'aec_prepare_siglens', 'aec_process_prepared',
@@ -105,6 +106,11 @@ def load():
     if LIB_PATH == _DEFAULT_LIB or hasattr(lib, 'aec_set_canceller_rescue'):   # absent from an older A/B build
         lib.aec_set_canceller_rescue.argtypes = [P, ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float]
         lib.aec_set_canceller_rescue.restype = ctypes.c_int
+    if LIB_PATH == _DEFAULT_LIB or hasattr(lib, 'aec_set_canceller_stereo'):   # absent from an older A/B build
+        lib.aec_set_canceller_stereo.argtypes = [P, ctypes.c_int32]
+        lib.aec_set_canceller_stereo.restype = ctypes.c_int
+        lib.aec_process_stereo.argtypes = [P, P, P, P, P, P, ctypes.c_int32, ctypes.c_int64, P, ctypes.c_int64, P, P]
+        lib.aec_process_stereo.restype = ctypes.c_int
     lib.aec_process.argtypes = [P, P, P, P, P, ctypes.c_int32, ctypes.c_int64, P, ctypes.c_int64, P, P]
     lib.aec_process.restype = ctypes.c_int
     lib.aec_process_siglens.argtypes = [P, P, P, P, P, ctypes.c_int32, ctypes.c_int64, P, ctypes.c_int64, P, P]
@@ -283,6 +289,7 @@ class Handle:
         self.h = h
         self.device = device
         self.rescue = False                # the Kalman canceller's rescue is on (set_canceller_rescue)
+        self.stereo = False                # the far end has two channels (set_canceller_stereo)
 
     def set_weights(self, blob):
         import numpy as np
@@ -301,12 +308,25 @@ class Handle:
         kind = {'nlms': 0, 'kalman': 1}.get(kind, kind)
         check(self.lib.aec_set_canceller(self.h, int(kind), float(a), float(p0)), self.h, 'aec_set_canceller')
         self.rescue = False                # every successful aec_set_canceller switches the rescue off
+        self.stereo = False                # ... and the stereo far end
 
     def set_canceller_rescue(self, on, mu=0.3, gamma=0.9, ratio=0.5):
         """The Kalman canceller's rescue from echo-path changes (aec_set_canceller_rescue)."""
         check(self.lib.aec_set_canceller_rescue(self.h, int(bool(on)), float(mu), float(gamma), float(ratio)), self.h,
               'aec_set_canceller_rescue')
         self.rescue = bool(on)
+
+    def set_canceller_stereo(self, on=True):
+        """The Kalman canceller over a two-channel far end, taps per channel (aec_set_canceller_stereo)."""
+        check(self.lib.aec_set_canceller_stereo(self.h, int(bool(on))), self.h, 'aec_set_canceller_stereo')
+        self.stereo = bool(on)
+
+    def process_stereo(self, mic_ptr, ref_l_ptr, ref_r_ptr, near_ptr, lengths, B, ld, out_ptr, ld_out, loss_ptr, stream):
+        """aec_process_stereo: lengths [B], one length per stream shared by the mic and both channels."""
+        import numpy as np
+        lens = np.ascontiguousarray(lengths, dtype=np.int64)
+        check(self.lib.aec_process_stereo(self.h, mic_ptr, ref_l_ptr, ref_r_ptr, near_ptr, lens.ctypes.data, int(B),
+                                          int(ld), out_ptr, int(ld_out), loss_ptr, stream), self.h, 'aec_process_stereo')
 
     def set_debug(self, on: bool):
         check(self.lib.aec_set_debug(self.h, int(bool(on))), self.h, 'aec_set_debug')

@@ -74,3 +74,8 @@ kalman_conf = {
 # powers smoothed with gamma, the shadow copied in when its error power falls
 # below ratio times the Kalman filter's.  1..8 taps, the batch path.
 kalman_rescue_conf = dict(kalman_conf, rescue=True, mu=0.3, gamma=0.9, ratio=0.5)
+
+# kalman_conf for a two-channel (stereo) far end (include/aec_hip.h
+# aec_set_canceller_stereo): 'taps' counts the taps per channel
+# (1..8), ref is [B, 2, N].  The batch path.
+kalman_stereo_conf = dict(kalman_conf, stereo=True)

@@ -144,6 +144,7 @@ class Little_net(nn.Module):
         self.linear1.apply(lambda m: self._kaiming(m, 'relu'))
         self.linear2.apply(lambda m: self._kaiming(m, 'sigmoid'))
         self.nlms = dict(nlms) if nlms else None
+        self.stereo = bool(self.nlms and self.nlms.get('stereo'))      # ref is [B, 2, N] (kalman_stereo_conf)
         self._handles = {}
         self._w_key = {}
         self._erb_key = {}
@@ -189,6 +190,10 @@ class Little_net(nn.Module):
                 if kind != 'kalman':
                     raise ValueError("nlms['rescue'] belongs to the Kalman canceller (kind='kalman')")
                 h.set_canceller_rescue(True, nl.get('mu', 0.3), nl.get('gamma', 0.9), nl.get('ratio', 0.5))
+            if nl.get('stereo'):
+                if kind != 'kalman':
+                    raise ValueError("nlms['stereo'] belongs to the Kalman canceller (kind='kalman')")
+                h.set_canceller_stereo(True)
             self._handles[idx] = h
         if not upload:
             return h, idx
@@ -211,7 +216,8 @@ class Little_net(nn.Module):
 
     # --- forward --------------------------------------------------------------
     def forward(self, mic, ref, near, erb):
-        """(ERB.py:252-334) mic/ref/near [B, N] (or [N]) float32 on a HIP device."""
+        """(ERB.py:252-334) mic/ref/near [B, N] (or [N]) float32 on a HIP device; with a
+        stereo far end (``nlms['stereo']``) ref is [B, 2, N] (or [2, N] beside a 1-D mic)."""
         if mic.dim() == 1:
             mic, ref, near = mic[None], ref[None], near[None] if near is not None else None
         if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self._params()):
@@ -266,6 +272,10 @@ class Little_net(nn.Module):
         if dev.type != 'cuda':
             raise RuntimeError(f'Little_net (gfx950) needs its inputs on a HIP device, got {dev}; '
                                'there is no CPU path')
+        if self.stereo:
+            return self._forward_stereo(mic, ref, near, erb, lengths, lookahead)
+        if ref.dim() == 3:
+            raise ValueError("ref is [B, 2, N] but this net takes one far-end channel (nlms['stereo'] is not set)")
         tens = [mic, ref] + ([near] if near is not None else [])
         for t in tens:
             if t.shape != mic.shape or t.device != dev:
@@ -300,6 +310,45 @@ class Little_net(nn.Module):
                           stream, token=lookahead or 0)
         return out, loss
 
+    def _forward_stereo(self, mic, ref, near, erb, lengths, lookahead):
+        """forward_ragged of a stereo net (aec_process_stereo): mic / near [B, N], ref [B, 2, N]
+        (left, right), lengths [B] shared by the mic and both channels."""
+        dev = mic.device
+        if lookahead:
+            raise NotImplementedError('a stereo net takes no look-ahead normaliser pass')
+        if mic.dim() != 2 or ref.dim() != 3 or ref.shape[1] != 2:
+            raise ValueError(f'a stereo net takes mic [B, N] and ref [B, 2, N], got {tuple(mic.shape)} and '
+                             f'{tuple(ref.shape)}')
+        B, L = mic.shape
+        if ref.shape != (B, 2, L) or ref.device != dev or (near is not None and (near.shape != mic.shape or
+                                                                                 near.device != dev)):
+            raise ValueError('mic, both channels of ref and near must share length and device')
+        if erb.shape != (257, 32):
+            raise ValueError(f'erb must be [257, 32], got {tuple(erb.shape)}')
+        lengths = np.asarray(lengths, dtype=np.int64)
+        if lengths.shape == (B, 3):
+            raise NotImplementedError('a stereo net takes one length per row ([B]), not per-signal lengths')
+        if lengths.shape != (B,) or (lengths < 1).any() or (lengths > L).any():
+            raise ValueError('lengths must be [B] with 1 <= length <= N')
+        mic = mic.contiguous().float()
+        ref_l = ref[:, 0].contiguous().float()      # two [B, N] tensors on one row stride
+        ref_r = ref[:, 1].contiguous().float()
+        near = near.contiguous().float() if near is not None else None
+        h, idx = self._handle(dev)
+        self._sync_erb(h, idx, erb)
+        lout = HOP * (int(lengths.max()) // HOP) if B > 0 else 0
+        out = torch.zeros(B, lout, device=dev, dtype=torch.float32) if B > 0 and (lengths != lengths.max()).any() \
+            else torch.empty(B, lout, device=dev, dtype=torch.float32)
+        loss = torch.empty(B, device=dev, dtype=torch.float32) if near is not None else None
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if B > 0:
+            with torch.cuda.device(dev):
+                h.process_stereo(mic.data_ptr(), ref_l.data_ptr(), ref_r.data_ptr(),
+                                 near.data_ptr() if near is not None else None, lengths, B, L,
+                                 out.data_ptr() if lout > 0 else None, max(lout, 1),
+                                 loss.data_ptr() if loss is not None else None, stream)
+        return out, loss
+
     def prepare_ragged(self, mic, ref, near, lengths, producer=None):
         """Queue the normaliser pass (ERB.py:254-256) of a batch a later
         ``forward_ragged(..., lookahead=token)`` on this net takes, on the
@@ -312,6 +361,8 @@ class Little_net(nn.Module):
         The tensors are recorded on the current stream, so the caching
         allocator does not hand their memory out while the pass reads it.
         Outputs are bit-identical with and without the look-ahead."""
+        if self.stereo:
+            raise NotImplementedError('a stereo net takes no look-ahead normaliser pass')
         dev = mic.device
         if dev.type != 'cuda':
             raise RuntimeError(f'Little_net (gfx950) needs its inputs on a HIP device, got {dev}')
@@ -344,6 +395,8 @@ class Little_net(nn.Module):
         (``stream_rescue_counts``)."""
         if torch.is_grad_enabled() and self.training:
             raise NotImplementedError('streaming is inference-only: use net.eval() and torch.no_grad()')
+        if self.stereo:
+            raise NotImplementedError('a stereo far end runs on the batch path only (forward / forward_ragged)')
         device = torch.device(device or 'cuda')
         if device.type != 'cuda':
             raise RuntimeError(f'Little_net (gfx950) streams live on a HIP device, got {device}')
@@ -444,10 +497,12 @@ class Little_net(nn.Module):
     def debug_intermediate(self, what, B, T, device=None):
         """Copy an intermediate of the last forward: 'mic_erb', 'ref_erb',
         'near_erb', 'gru_out', 'mask', 'est_erb' -> [B, T, 32]; 'rescue_mask' (the
-        canceller rescue's copy decisions, 1 = the shadow was copied) -> [B, T, 257]."""
-        codes = dict(mic_erb=0, ref_erb=1, near_erb=2, gru_out=3, mask=4, est_erb=5, rescue_mask=6)
+        canceller rescue's copy decisions, 1 = the shadow was copied) -> [B, T, 257];
+        'error_spec' (the linear stage's output E as (re, im) pairs, slot 0 the real pair
+        (E[0], E[256])) -> [B, T, 512]."""
+        codes = dict(mic_erb=0, ref_erb=1, near_erb=2, gru_out=3, mask=4, est_erb=5, rescue_mask=6, error_spec=7)
         device = torch.device(device or 'cuda')
         h, _ = self._handle(device)
-        dst = torch.empty(B, T, 257 if what == 'rescue_mask' else 32, device=device, dtype=torch.float32)
+        dst = torch.empty(B, T, dict(rescue_mask=257, error_spec=512).get(what, 32), device=device, dtype=torch.float32)
         h.debug_copy(codes[what], dst.data_ptr(), dst.numel(), torch.cuda.current_stream(device).cuda_stream)
         return dst

@@ -103,6 +103,40 @@ def scene_path_change(n, seed, double_talk=True, change_at=None, return_echo=Fal
     return out
 
 
+def scene_stereo(n, seed, double_talk=True, pan=((1.0, 0.3), (0.3, 1.0)), return_echo=False):
+    """scene() with two loudspeakers: float32 (mic, ref [2, n], near[, echo]).  One far-end
+    source per entry of ``pan`` = (gain into left, gain into right); the sources are
+    independent (source 0 under a 4 Hz envelope, the others 3.1 Hz).  Draws, in order:
+    every source, h_l = rir, h_r = rir, then near and noise as scene does.  Left and right
+    share the one factor that puts their downmix 0.5 (l + r) at 0.1 RMS, echo =
+    l * h_l + r * h_r at -6 dB relative to that, near and noise relative to it too."""
+    from scipy.signal import fftconvolve
+    rng = np.random.default_rng(seed)
+    src = [_ar1(rng, n) * _envelope(rng, n, rate_hz=4.0 if i == 0 else 3.1) for i in range(len(pan))]
+    l = sum(p[0] * s for p, s in zip(pan, src))
+    r = sum(p[1] * s for p, s in zip(pan, src))
+    g = 0.1 / _rms(0.5 * (l + r))
+    l, r = l * g, r * g
+    level = _rms(0.5 * (l + r))
+    h_l = rir(rng)
+    h_r = rir(rng)
+    echo = (fftconvolve(l, h_l) + fftconvolve(r, h_r))[:n]
+    echo *= (level * 10 ** (-6 / 20)) / _rms(echo)
+    if double_talk:
+        near = _ar1(rng, n, a=0.7) * _envelope(rng, n, rate_hz=2.5)
+        gate = (np.sin(2 * np.pi * 0.4 * np.arange(n) / SR + rng.uniform(0, 6.28)) > 0.2)
+        near *= gate
+        near *= (level * 10 ** (-3 / 20)) / max(_rms(near), 1e-12)
+    else:
+        near = np.zeros(n)
+    noise = rng.standard_normal(n) * level * 10 ** (-50 / 20)
+    mic = echo + near + noise
+    out = (mic.astype(np.float32), np.stack([l, r]).astype(np.float32), near.astype(np.float32))
+    if return_echo:
+        out = out + (echo.astype(np.float32),)
+    return out
+
+
 def batch(B, n, seed0=0, double_talk=True):
     """[B, n] float32 arrays (mic, ref, near) with per-stream seeds seed0+b."""
     mic = np.empty((B, n), np.float32)

@@ -92,6 +92,12 @@ struct aec_handle {
     CancellerRescue rescue;
     float* d_rmask = nullptr;    // [B][T][257]
     size_t rmask_cap = 0;        // floats
+    // a two-channel far end (aec_set_canceller_stereo, aec_process_stereo): allocated for a stereo handle only
+    int stereo = 0;
+    double2* d_smom = nullptr;   // [B][3][kMomChunks] moment partials of (left, right, -)
+    int64_t smom_cap = 0;        // streams
+    float2* d_srows = nullptr;   // [2][srows_cap / 2] rows of the two normalised channels, [B][T][256] each
+    size_t srows_cap = 0;        // float2 elements
     std::vector<int64_t> last_lens;                 // [B][3] of the last call (work lists rebuilt on change)
     int debug = 0;
     int gru_mode = 0;            // AEC_GRU_MODE (A/B builds: timing experiments; results invalid unless 0)
@@ -281,6 +287,7 @@ const char* aec_build_info(void) {
     static const std::string info = std::string("arch=gfx950 ab_knobs=") + (AEC_AB_BUILD ? "on" : "off") +
                                     " canceller_rescue=kalman:1-" + std::to_string(aec::kRescueMaxTaps) +
                                     " stream_rescue=kalman:1-" + std::to_string(aec::kRescueMaxTaps) +
+                                    " canceller_stereo=kalman:1-" + std::to_string(aec::kStereoMaxTaps) +
                                     " mode_knobs=" + aec::kModeKnobs;
     return info.c_str();
 }
@@ -308,6 +315,17 @@ aec_status aec_set_canceller(aec_handle* h, int32_t kind, float a, float p0) {
     }
     h->canc.kind = kind;
     h->rescue.on = 0;
+    h->stereo = 0;
+    return AEC_OK;
+}
+
+aec_status aec_set_canceller_stereo(aec_handle* h, int32_t on) {
+    if (!h) return AEC_ERR_INVALID_ARG;
+    bool unsupported = false;
+    const std::string why = check_canceller_stereo(h->cfg.nlms_taps, h->canc.kind, on, h->rescue.on != 0,
+                                                   h->d_state != nullptr, &unsupported);
+    if (!why.empty()) return fail(h, unsupported ? AEC_ERR_UNSUPPORTED : AEC_ERR_INVALID_ARG, why);
+    h->stereo = on != 0;
     return AEC_OK;
 }
 
@@ -315,7 +333,7 @@ aec_status aec_set_canceller_rescue(aec_handle* h, int32_t on, float mu, float g
     if (!h) return AEC_ERR_INVALID_ARG;
     bool unsupported = false;
     const std::string why = check_canceller_rescue(h->cfg.nlms_taps, h->canc.kind, on, mu, gamma, ratio,
-                                                   h->d_state != nullptr, &unsupported);
+                                                   h->d_state != nullptr, &unsupported, h->stereo != 0);
     if (!why.empty()) return fail(h, unsupported ? AEC_ERR_UNSUPPORTED : AEC_ERR_INVALID_ARG, why);
     if (on) h->rescue = CancellerRescue{1, mu, gamma, ratio};
     else h->rescue.on = 0;
@@ -544,14 +562,31 @@ aec_status aec_process(aec_handle* h, const float* mic, const float* ref, const 
     return aec_process_siglens(h, mic, ref, near, l3.data(), B, ld, out, ld_out, loss, stream);
 }
 
+// ref_r: the right far-end channel of aec_process_stereo (ref is then the left), null in every other call
 static aec_status process_impl(aec_handle* h, uint64_t token, const float* mic, const float* ref, const float* near,
                                const int64_t* lengths3, int32_t B, int64_t ld, float* out, int64_t ld_out,
-                               float* loss, void* stream);
+                               float* loss, void* stream, const float* ref_r = nullptr);
 
 aec_status aec_process_siglens(aec_handle* h, const float* mic, const float* ref, const float* near,
                                const int64_t* lengths3, int32_t B, int64_t ld, float* out, int64_t ld_out,
                                float* loss, void* stream) {
     return process_impl(h, 0, mic, ref, near, lengths3, B, ld, out, ld_out, loss, stream);
+}
+
+static const char kStereoOnly[] = "a stereo handle (aec_set_canceller_stereo) takes its batches through aec_process_stereo";
+static const char kStereoNoStream[] = "a stereo handle (aec_set_canceller_stereo) has no streaming state: aec_process_stereo is its only path";
+
+aec_status aec_process_stereo(aec_handle* h, const float* mic, const float* ref_l, const float* ref_r, const float* near,
+                              const int64_t* lengths, int32_t B, int64_t ld, float* out, int64_t ld_out, float* loss,
+                              void* stream) {
+    if (!h) return AEC_ERR_INVALID_ARG;
+    if (!h->stereo) return fail(h, AEC_ERR_INVALID_ARG, "aec_set_canceller_stereo first");
+    if (B < 0 || !lengths) return fail(h, AEC_ERR_INVALID_ARG, "bad batch / lengths");
+    if (B == 0) return AEC_OK;
+    if (!ref_r) return fail(h, AEC_ERR_INVALID_ARG, "null ref_r");
+    std::vector<int64_t> l3((size_t)B * 3);
+    for (int b = 0; b < B; ++b) l3[3 * b] = l3[3 * b + 1] = l3[3 * b + 2] = lengths[b];
+    return process_impl(h, 0, mic, ref_l, near, l3.data(), B, ld, out, ld_out, loss, stream, ref_r);
 }
 
 aec_status aec_process_prepared(aec_handle* h, uint64_t token, const float* mic, const float* ref, const float* near,
@@ -564,8 +599,9 @@ aec_status aec_process_prepared(aec_handle* h, uint64_t token, const float* mic,
 
 static aec_status process_impl(aec_handle* h, uint64_t token, const float* mic, const float* ref, const float* near,
                                const int64_t* lengths3, int32_t B, int64_t ld, float* out, int64_t ld_out,
-                               float* loss, void* stream) {
+                               float* loss, void* stream, const float* ref_r) {
     if (!h) return AEC_ERR_INVALID_ARG;
+    if (h->stereo && !ref_r) return fail(h, AEC_ERR_UNSUPPORTED, kStereoOnly);
     if (!h->have_w || !h->have_erb) return fail(h, AEC_ERR_INVALID_ARG, "weights / erb not set");
     if (B < 0 || !lengths3) return fail(h, AEC_ERR_INVALID_ARG, "bad batch / lengths");
     if (B == 0) return AEC_OK;
@@ -581,7 +617,8 @@ static aec_status process_impl(aec_handle* h, uint64_t token, const float* mic, 
     AEC_ON_DEVICE(h);
     // which kernels run (aec_host.h); AEC_GRU_NS is a mode knob read per call
     const Plan p = plan_call({h->cfg.nlms_taps, B, h->small_b, h->nlms_mode, h->small_pipe, h->fused, h->gru_mode,
-                              h->num_cus, AEC_MODE_KNOB("AEC_GRU_NS", 0), token != 0, h->canc.kind, h->rescue.on});
+                              h->num_cus, AEC_MODE_KNOB("AEC_GRU_NS", 0), token != 0, h->canc.kind, h->rescue.on,
+                              h->stereo});
     if (p.nlms_batch && nlms_smem_bytes(h->sched_len, h->cfg.nlms_taps) > 160 * 1024)   // before any launch
         return fail(h, AEC_ERR_UNSUPPORTED, "erb schedule too long for the NLMS kernel's LDS budget");
     // aec_process_prepared: the look-ahead pass named by `token` (aec_prepare_siglens), checked
@@ -638,6 +675,21 @@ static aec_status process_impl(aec_handle* h, uint64_t token, const float* mic, 
             if (s != AEC_OK) return s;
         }
     }
+    // a stereo call: the moment partials and the rows of the two far-end channels
+    const int64_t chan_stride = (int64_t)B * Tmax * 256;
+    if (h->stereo) {
+        if (!p.split || p.pipe || !p.fold_norm) return fail(h, AEC_ERR_UNSUPPORTED, "a stereo call runs on the split plan only");
+        if (B > h->smom_cap) {
+            s = grow_after_last(h, h->d_smom, h->smom_cap, (int64_t)B, (size_t)B * 3 * kMomChunks * sizeof(double2));
+            if (s != AEC_OK) return s;
+        }
+        if (2 * (size_t)chan_stride > h->srows_cap) {
+            s = grow_after_last(h, h->d_srows, h->srows_cap, 2 * (size_t)chan_stride,
+                                2 * (size_t)chan_stride * sizeof(float2));
+            if (s != AEC_OK) return s;
+        }
+        HIP_TRY(h, launch_moments(ref, ref_r, nullptr, ld, h->d_slen, h->d_smom, 0, B, 2, st));
+    }
     const bool rmask = p.split && h->rescue.on && h->debug;      // the rescue's copy decisions, for aec_debug_copy
     if (rmask && (size_t)B * Tmax * 257 > h->rmask_cap) {
         const size_t need = (size_t)B * Tmax * 257;
@@ -678,7 +730,17 @@ static aec_status process_impl(aec_handle* h, uint64_t token, const float* mic, 
         HIP_TRY(h, launch_analysis(a, st));
         if (p.split && !p.pipe) {      // few streams: recursion per stream, then mic_erb frame-parallel
             const RecursionArgs ra{h->d_rows, h->d_spec, h->d_len, Tmax, 0, B, h->d_rows + (size_t)B * Tmax * 512};
-            if (h->rescue.on)
+            if (h->stereo) {
+                // both channels' rows and the downmix's ref_erb (over K2's, which saw the left channel alone)
+                StereoRowsArgs sa{};
+                sa.sig[0] = ref; sa.sig[1] = ref_r; sa.ld = ld; sa.items = h->d_items; sa.nitems = a.nitems;
+                sa.mom = h->d_smom; sa.tables = reinterpret_cast<const float*>(h->d_tab);
+                sa.rows = h->d_srows; sa.chan_stride = chan_stride; sa.Tmax = Tmax;
+                HIP_TRY(h, launch_stereo_rows(sa, st));
+                HIP_TRY(h, launch_stereo_ref_erb(h->d_srows, chan_stride, h->d_feats, Tmax, h->d_sched, h->sched_len,
+                                                 h->d_items, a.nitems, st));
+                HIP_TRY(h, launch_recursion_stereo(ra, h->d_srows, chan_stride, h->canceller(), st));
+            } else if (h->rescue.on)
                 HIP_TRY(h, launch_recursion_rescue(ra, h->canceller(), h->rescue, rmask ? h->d_rmask : nullptr, st));
             else
                 HIP_TRY(h, launch_recursion(ra, h->canceller(), st));
@@ -737,6 +799,7 @@ aec_status aec_prepare_siglens(aec_handle* h, const float* mic, const float* ref
                                const int64_t* lengths3, int32_t B, int64_t ld, void* stream, uint64_t* token) {
     if (!h) return AEC_ERR_INVALID_ARG;
     if (token) *token = 0;
+    if (h->stereo) return fail(h, AEC_ERR_UNSUPPORTED, std::string(kStereoOnly) + ", which takes no look-ahead");
     if (B <= 0 || !lengths3 || !mic || !ref) return fail(h, AEC_ERR_INVALID_ARG, "bad batch / lengths / signals");
     if (h->ring.full()) return fail(h, AEC_ERR_INVALID_ARG, "two look-ahead batches already pending");
     const int nsig = near ? 3 : 2;
@@ -786,10 +849,12 @@ aec_status aec_prepare(aec_handle* h, const float* mic, const float* ref, const 
 aec_status aec_debug_copy(aec_handle* h, int32_t what, float* dst, size_t n, void* stream) {
     if (!h) return AEC_ERR_INVALID_ARG;
     const int64_t B = h->last_B, T = h->last_T;
-    if (!dst || n < (size_t)(B * T * (what == 6 ? 257 : 32))) return fail(h, AEC_ERR_INVALID_ARG, "dst too small");
+    if (!dst || n < (size_t)(B * T * (what == 6 ? 257 : what == 7 ? 512 : 32))) return fail(h, AEC_ERR_INVALID_ARG, "dst too small");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     AEC_ON_DEVICE(h);
-    if (what < 0 || what > 6) return fail(h, AEC_ERR_INVALID_ARG, "unknown intermediate");
+    if (what < 0 || what > 7) return fail(h, AEC_ERR_INVALID_ARG, "unknown intermediate");
+    if (what == 7 && (!h->d_spec || B * T == 0))
+        return fail(h, AEC_ERR_INVALID_ARG, "error_spec: a handle with a linear stage (nlms_taps > 0), after aec_process");
     if (what == 6 && (!h->debug || !h->rescue.on || (size_t)(B * T * 257) > h->rmask_cap || B * T == 0))
         return fail(h, AEC_ERR_INVALID_ARG, "rescue_mask: aec_set_canceller_rescue and aec_set_debug before aec_process");
     if ((what == 3 || what == 4) && !h->debug) return fail(h, AEC_ERR_INVALID_ARG, "enable aec_set_debug before aec_process");
@@ -802,6 +867,8 @@ aec_status aec_debug_copy(aec_handle* h, int32_t what, float* dst, size_t n, voi
                                     32 * sizeof(float), B * T, hipMemcpyDeviceToDevice, st));
     } else if (what == 6) {
         HIP_TRY(h, hipMemcpyAsync(dst, h->d_rmask, B * T * 257 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    } else if (what == 7) {
+        HIP_TRY(h, hipMemcpyAsync(dst, h->d_spec, B * T * 256 * sizeof(float2), hipMemcpyDeviceToDevice, st));
     } else if (what == 3 || what == 4) {
         if (!h->debug) return fail(h, AEC_ERR_INVALID_ARG, "enable aec_set_debug before aec_process");
         HIP_TRY(h, hipMemcpyAsync(dst, h->d_dbg + (what - 3) * B * T * 32, B * T * 32 * sizeof(float),
@@ -871,6 +938,7 @@ static aec_status stream_open_state(aec_handle* h, int32_t B, bool rescue) {
 aec_status aec_stream_open(aec_handle* h, int32_t B) {
     if (!h) return AEC_ERR_INVALID_ARG;
     if (B < 1) return fail(h, AEC_ERR_INVALID_ARG, "stream count must be >= 1");
+    if (h->stereo) return fail(h, AEC_ERR_UNSUPPORTED, kStereoNoStream);
     if (h->rescue.on) return fail(h, AEC_ERR_UNSUPPORTED, "this state has no rows for the canceller rescue's shadow filter: aec_stream_open_rescue opens a rescue handle's streams");
     AEC_ON_DEVICE(h);
     return stream_open_state(h, B, false);
@@ -878,6 +946,7 @@ aec_status aec_stream_open(aec_handle* h, int32_t B) {
 
 aec_status aec_stream_open_rescue(aec_handle* h, int32_t B) {
     if (!h) return AEC_ERR_INVALID_ARG;
+    if (h->stereo) return fail(h, AEC_ERR_UNSUPPORTED, kStereoNoStream);
     if (!h->rescue.on) return fail(h, AEC_ERR_INVALID_ARG, "the canceller rescue is not on for this handle (aec_set_canceller_rescue)");
     if (B < 1) return fail(h, AEC_ERR_INVALID_ARG, "stream count must be >= 1");
     AEC_ON_DEVICE(h);
@@ -1216,6 +1285,7 @@ void aec_destroy(aec_handle* h) {
     (void)hipFree(h->d_mom); (void)hipFree(h->d_cvals); (void)hipFree(h->d_lists);
     (void)hipFree(h->d_feats); (void)hipFree(h->d_est); (void)hipFree(h->d_dbg); (void)hipFree(h->d_spec);
     (void)hipFree(h->d_state); (void)hipFree(h->d_rows); (void)hipFree(h->d_progress); (void)hipFree(h->d_rmask);
+    (void)hipFree(h->d_smom); (void)hipFree(h->d_srows);
     (void)hipFree(h->d_track); (void)hipFree(h->d_drift_tab); (void)hipFree(h->d_dtrack);
     if (h->h_pipe_err) (void)hipHostFree(h->h_pipe_err);
     (void)hipFree(h->d_th); (void)hipFree(h->d_tloss); (void)hipFree(h->d_rec); (void)hipFree(h->d_dg);

@@ -76,8 +76,12 @@ static_assert(std::is_trivially_copyable<CancellerRescue>::value, "CancellerResc
 // aec_set_canceller_rescue's argument rules, as check_canceller states aec_set_canceller's.  kind:
 // the handle's selected canceller.  The values are checked only when the call switches the rescue on.
 inline std::string check_canceller_rescue(int taps, int kind, int on, float mu, float gamma, float ratio,
-                                          bool stream_open, bool* unsupported) {
+                                          bool stream_open, bool* unsupported, bool stereo = false) {
     *unsupported = false;
+    if (stereo && on) {                    // the stereo recursion (aec_stereo.hip) has no shadow filter
+        *unsupported = true;
+        return "the canceller rescue does not exist for a stereo handle (aec_set_canceller_stereo)";
+    }
     if (kind != kCancellerKalman) return "the rescue belongs to the Kalman canceller: select it with aec_set_canceller first";
     if (taps < 1 || taps > kRescueMaxTaps) {
         *unsupported = true;
@@ -88,6 +92,29 @@ inline std::string check_canceller_rescue(int taps, int kind, int on, float mu, 
         if (!(mu >= 0.f && std::isfinite(mu))) return "rescue step size mu must be finite and >= 0";
         if (!(gamma >= 0.f && gamma < 1.f)) return "rescue smoothing factor gamma must be in [0, 1)";
         if (!(ratio >= 0.f && std::isfinite(ratio))) return "rescue ratio must be finite and >= 0";
+    }
+    return "";
+}
+
+// The Kalman canceller for a two-channel far end (aec_set_canceller_stereo): taps
+// per channel, the two channels' histories side by side in one filter with per-tap covariances,
+// which is the 2 taps chain of KalmanHalf<2 taps> with half 0 fed the left channel's rows and
+// half 1 the right's (aec_stereo.hip).  The batch path only.
+constexpr int kStereoMaxTaps = 8;      // taps per channel the stereo recursion is instantiated for
+// aec_set_canceller_stereo's argument rules, as check_canceller_rescue states the rescue's.  kind:
+// the handle's selected canceller; rescue: its rescue is on.
+inline std::string check_canceller_stereo(int taps, int kind, int on, bool rescue, bool stream_open, bool* unsupported) {
+    (void)on;                              // the rules are the same for switching it on and off
+    *unsupported = false;
+    if (kind != kCancellerKalman) return "the stereo far end belongs to the Kalman canceller: select it with aec_set_canceller first";
+    if (taps < 1 || taps > kStereoMaxTaps) {
+        *unsupported = true;
+        return "the stereo canceller exists for 1..8 taps per channel";
+    }
+    if (stream_open) return "a streaming state is open: the streaming kernels take one far-end channel";
+    if (rescue) {
+        *unsupported = true;
+        return "the stereo canceller has no rescue: switch it off first (aec_set_canceller_rescue)";
     }
     return "";
 }

@@ -467,6 +467,7 @@ struct PlanIn {
     bool lookahead;     // the call consumes a look-ahead normaliser pass
     int kalman = 0;     // the canceller is the Kalman filter (aec_set_canceller): the pipeline is not built for it
     int rescue = 0;     // the Kalman canceller's rescue is on (aec_set_canceller_rescue): the split plan only
+    int stereo = 0;     // a two-channel far end (aec_set_canceller_stereo, aec_process_stereo): the split plan only
 };
 struct Plan {
     bool nlms_batch;    // K2n: one block per stream runs transforms + recursion
@@ -481,16 +482,17 @@ struct Plan {
 inline Plan plan_call(const PlanIn& in) {
     // 9..16 taps: the long-tail recursion (aec_longtail.hip) exists for the split plan only, so
     // these calls take it at every B and never K2n or the pipeline.  The same holds for a handle
-    // with the canceller rescue on: its recursion (aec_rescue.hip) is a split-plan kernel
-    const bool only_split = in.nlms_taps > kK2nMaxTaps || (in.rescue && in.nlms_taps > 0);
+    // with the canceller rescue on: its recursion (aec_rescue.hip) is a split-plan kernel, and for
+    // a stereo handle, whose recursion (aec_stereo.hip) reads a row per far-end channel
+    const bool only_split = in.nlms_taps > kK2nMaxTaps || ((in.rescue || in.stereo) && in.nlms_taps > 0);
     const bool small = (in.B <= in.small_b && in.nlms_mode == 0) || only_split;
     const bool fused = in.fused && in.gru_mode == 0;
     const bool half = 2 * (int64_t)in.B <= (int64_t)in.num_cus;
     Plan p;
     p.nlms_batch = in.nlms_taps > 0 && !small;
     p.split = in.nlms_taps > 0 && small;
-    p.pipe = in.small_pipe && in.nlms_taps == kPipeTaps && !in.kalman && !in.rescue && small && fused && half &&
-             in.gru_ns != 2;
+    p.pipe = in.small_pipe && in.nlms_taps == kPipeTaps && !in.kalman && !in.rescue && !in.stereo && small && fused &&
+             half && in.gru_ns != 2;
     p.bypass_fused = in.nlms_taps == 0 && fused && half;
     p.fold_norm = (p.split || p.bypass_fused) && !in.lookahead;
     p.gru_one = in.gru_ns == 1 || (in.gru_ns != 2 && 2 * (int64_t)in.B <= (int64_t)std::max(in.num_cus, 2));

@@ -187,6 +187,26 @@ hipError_t launch_recursion_long(const RecursionArgs& a, const Canceller& c, hip
 // frame; frames past a stream's end are left as they are), the debug instantiation.
 hipError_t launch_recursion_rescue(const RecursionArgs& a, const Canceller& c, const CancellerRescue& r, float* mask,
                                    hipStream_t st);
+// A two-channel far end (aec_stereo.hip; aec_process_stereo): the rows of the two normalised
+// channels, the ref_erb feature of their downmix spectrum, and the Kalman recursion with taps per
+// channel (1..kStereoMaxTaps), which reads the mic row of K2's packed rows and a row per channel.
+struct StereoRowsArgs {
+    const float* sig[2];     // left, right: [B][ld], every row with the mic's length
+    int64_t ld;
+    const WorkItem* items;   // K2's work list (4-frame items)
+    int64_t nitems;
+    const double2* mom;      // [B][3][kMomChunks] moment partials of (left, right, -)
+    const float* tables;     // DevTables
+    float2* rows;            // out: [2][B][Tmax][256] (slot 0 = (X[0], X[256]))
+    int64_t chan_stride;     // float2 between the channels' rows (>= B * Tmax * 256)
+    int64_t Tmax;
+};
+hipError_t launch_stereo_rows(const StereoRowsArgs& a, hipStream_t st);
+// feats[b][t][32:64] = ERB(|0.5 (S_L + S_R)|) from the two rows
+hipError_t launch_stereo_ref_erb(const float2* rows, int64_t chan_stride, float* feats, int64_t Tmax, const float* sched,
+                                 int sched_len, const WorkItem* items, int64_t nitems, hipStream_t st);
+hipError_t launch_recursion_stereo(const RecursionArgs& a, const float2* far, int64_t chan_stride, const Canceller& c,
+                                   hipStream_t st);
 hipError_t launch_mic_erb(const float2* spec, float* feats, const int64_t* lens, int64_t Tmax, const float* sched,
                           int sched_len, const WorkItem* items, int64_t nitems, hipStream_t st);
 hipError_t launch_gru(const GruArgs& a, int B, hipStream_t st);

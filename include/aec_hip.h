@@ -123,6 +123,27 @@ aec_status aec_set_canceller(aec_handle* h, int32_t kind, float a, float p0);
  * AEC_ERR_UNSUPPORTED. */
 aec_status aec_set_canceller_rescue(aec_handle* h, int32_t on, float mu, float gamma, float ratio);
 
+/* A two-channel (stereo) far end for the Kalman canceller, off unless
+ * switched on here.  The microphone then hears x_L * h_L + x_R * h_R, which a canceller
+ * fed the downmix cannot model; with stereo on, nlms_taps counts the taps PER CHANNEL
+ * (1..8) and the filter runs over both channels' histories, R_c,l = R_c[t-l]:
+ *   E = D - sum_c sum_l W[c][l] R_c,l,  psi = beta psi + (1-beta) |E|^2,
+ *   S = sum_c sum_l P[c][l] |R_c,l|^2 + psi + delta,  G_c,l = P[c][l] / S,
+ *   W[c][l] = a (W[c][l] + G_c,l conj(R_c,l) E),
+ *   P[c][l] = a^2 (1 - G_c,l |R_c,l|^2) P[c][l] + (1 - a^2) |W[c][l]|^2
+ * (W = 0, P = p0, psi = 0 at each stream start).  Each channel is normalised by its
+ * own constant, as ref is; the post-filter's ref_erb feature is that of the downmix
+ * spectrum 0.5 (S_L + S_R) (for L == R the mono feature, bit for bit).  A stereo
+ * handle takes its batches through aec_process_stereo alone, on the K2 / per-stream
+ * recursion / mic_erb kernels at every batch size: aec_process, aec_process_siglens,
+ * aec_prepare*, aec_process_prepared, aec_stream_open and aec_stream_open_rescue
+ * return AEC_ERR_UNSUPPORTED.  on = 0 switches it off, as does every later
+ * successful aec_set_canceller.
+ * AEC_ERR_INVALID_ARG: the Kalman canceller is not selected, or a streaming state is
+ * open.  AEC_ERR_UNSUPPORTED: nlms_taps > 8, or the canceller rescue is on (and
+ * aec_set_canceller_rescue(on != 0) on a stereo handle returns AEC_ERR_UNSUPPORTED). */
+aec_status aec_set_canceller_stereo(aec_handle* h, int32_t on);
+
 aec_status aec_set_weights(aec_handle* h, const float* weights, size_t n_weights);
 aec_status aec_set_erb(aec_handle* h, const float* erb_257xbands);
 
@@ -139,6 +160,14 @@ aec_status aec_set_erb(aec_handle* h, const float* erb_257xbands);
 aec_status aec_process(aec_handle* h, const float* mic, const float* ref, const float* near,
                        const int64_t* lengths, int32_t B, int64_t ld,
                        float* out, int64_t ld_out, float* loss, void* stream);
+
+/* aec_process for a stereo handle (aec_set_canceller_stereo): ref_l, ref_r are the
+ * left and right far-end channels, device [B, ld] float32 each, row b of both
+ * holding lengths[b] valid samples; everything else as aec_process (near and loss
+ * may be NULL).  AEC_ERR_INVALID_ARG on a handle without stereo. */
+aec_status aec_process_stereo(aec_handle* h, const float* mic, const float* ref_l, const float* ref_r,
+                              const float* near, const int64_t* lengths, int32_t B, int64_t ld,
+                              float* out, int64_t ld_out, float* loss, void* stream);
 
 /* aec_process with a length per signal, as scripts/test.py feeds the
  * reference (test.py:139: default collate at batch 1, every signal at its
@@ -479,7 +508,10 @@ aec_status aec_drift_track_push(aec_handle* h, const float* mic, const float* re
  * what: 0 = mic_erb, 1 = ref_erb, 2 = near_erb, 3 = gru_out (h_t),
  *       4 = mask, 5 = est_erb;
  *       6 = rescue_mask: the canceller rescue's copy decisions of that call
- *       (aec_set_canceller_rescue), dst [B, T_max, 257] float32, 1 = copied. */
+ *       (aec_set_canceller_rescue), dst [B, T_max, 257] float32, 1 = copied;
+ *       7 = error_spec: the linear stage's output E of that call (nlms_taps > 0; no
+ *       aec_set_debug needed), dst [B, T_max, 256] pairs of float32 (re, im), slot 0
+ *       the real pair (E[0], E[256]). */
 aec_status aec_set_debug(aec_handle* h, int32_t enable);
 aec_status aec_debug_copy(aec_handle* h, int32_t what, float* dst, size_t n_floats, void* stream);
 
@@ -554,7 +586,8 @@ const char* aec_last_error(const aec_handle* h);
  * provenance).  "arch=gfx950 ab_knobs=off ... mode_knobs=<names>": ab_knobs=on marks
  * an A/B build (-DAEC_AB_KNOBS) that reads timing-only / work-skipping knobs;
  * canceller_rescue= and stream_rescue= name the canceller and tap range the batch
- * and the streaming rescue are built for; mode_knobs lists the environment
+ * and the streaming rescue are built for, canceller_stereo= those of the stereo
+ * far end (taps per channel); mode_knobs lists the environment
  * variables that select tested modes. */
 const char* aec_build_info(void);
 void aec_destroy(aec_handle* h);
