@@ -85,6 +85,45 @@ def forward_stereo(mic, ref, near, erb, w, cfg, **kw):
     return out, loss, dict(E=E, mic_erb=mic_erb, ref_erb=ref_erb, near_erb=near_erb)
 
 
+def delayed_copy_scene(n, taps, seed):
+    """A far end whose right channel is the left delayed by 256 taps samples, built so that a
+    stereo filter with `taps` per channel computes, operation for operation, what a mono
+    filter with 2 taps on the left channel computes: float32 (mic, ref [2, n], near).
+
+    The left channel x is a block q of coloured noise quantised to multiples of 2^-16
+    (|q| < 1), then -q, then zeros, all within the first n - 256 taps samples; the right is
+    256 taps zeros, then x[:n - 256 taps].  Each channel then sums to exactly zero with every
+    partial sum exact in double in any order, so the normaliser's mean / sd is exactly 0,
+    x - 0 = x, and the right channel's frame t holds the samples of the left's frame
+    t - taps (zeros before frame taps).  mic is x through synth.rir plus a little noise."""
+    from scipy.signal import fftconvolve
+
+    from aec_amd import synth
+    d = 256 * taps
+    half = (n - d) // 2
+    assert half >= 1, (n, taps)
+    rng = np.random.default_rng(seed)
+    q = synth._ar1(rng, half) * synth._envelope(rng, half)
+    q = np.round(np.clip(q * (0.1 / synth._rms(q)), -0.9, 0.9) * 65536.0) / 65536.0
+    x = np.zeros(n)
+    x[:half] = q
+    x[half:2 * half] = -q
+    right = np.zeros(n)
+    right[d:] = x[:n - d]
+    echo = fftconvolve(x, synth.rir(rng))[:n]
+    echo *= (0.1 * 10 ** (-6 / 20)) / synth._rms(echo)
+    near = synth._ar1(rng, n, a=0.7) * (0.1 * 10 ** (-3 / 20) / np.sqrt(1.0 / (1.0 - 0.49)))
+    mic = echo + near + rng.standard_normal(n) * 0.1 * 10 ** (-50 / 20)
+    ref = np.stack([x, right]).astype(np.float32)
+    # the construction's claims, on what the device will read
+    for c in ref.astype(np.float64):
+        assert np.array_equal(c * 65536.0, np.round(c * 65536.0)) and np.abs(c).max() < 1.0
+        assert c.sum() == 0.0 and np.sum(c[::-1]) == 0.0 and np.cumsum(c)[-1] == 0.0
+        assert c.any()
+    assert np.array_equal(ref[1, d:], ref[0, :n - d]) and not ref[1, :d].any() and not ref[0, n - d:].any()
+    return mic.astype(np.float32), ref, near.astype(np.float32)
+
+
 def echo_removed_db_stereo(mic, ref, echo, first_frame=30, E=None, **kw):
     """kalman_oracle.echo_removed_db for a stereo far end (ref: [2, n]):
     10 log10(sum |Se|^2 / sum |Se - Y|^2) over frames >= first_frame, Y = Sm - E the

@@ -108,3 +108,24 @@ def test_two_talkers_stereo_over_mono(seed, double_talk):
 @pytest.mark.parametrize('seed', SEEDS)
 def test_coherent_far_end_costs_little(seed, double_talk, pan):
     assert _gain(seed, double_talk, pan) >= -0.6
+
+
+@pytest.mark.parametrize('n,taps', [(600, 2), (2303, 4), (3000, 1), (5000, 3), (9001, 8)])
+def test_delayed_copy_is_the_mono_filter_of_twice_the_taps(n, taps):
+    """Right = left delayed by `taps` frames, both channels with an exactly zero normaliser
+    constant (delayed_copy_scene): the right channel's spectrum rows are the left's, `taps`
+    frames late, and the stereo filter with `taps` per channel is the mono filter with 2 taps
+    on the left channel, to the last bit.  The GPU test holds the kernels to the same."""
+    mic, ref, near = SO.delayed_copy_scene(n, taps, 9500 + n)
+    assert mic.dtype == ref.dtype == near.dtype == np.float32 and ref.shape == (2, n) and near.any()
+    for c in ref:
+        assert np.array_equal(O.normalise(c), c.astype(np.float64))            # mean / sd is exactly 0
+    Sm, Sl, Sr = SO.spectra(mic, ref)
+    T = n // 256 + 1
+    assert np.array_equal(Sr[taps:], Sl[:T - taps]) and not Sr[:taps].any() and Sl[:T - taps].any()
+    for kw in (dict(KW, taps=taps), dict(taps=taps, a=0.9, beta=0.8, delta=1e-3, p0=0.5)):
+        E = SO.kalman_stereo(Sm, Sl, Sr, **kw)
+        mono = KO.kalman(Sm, Sl, **dict(kw, taps=2 * taps))
+        assert np.array_equal(E, mono) and np.abs(E).max() > 0
+        if T >= taps + 2:                                                      # the first frame a tap more can move E
+            assert not np.array_equal(E, KO.kalman(Sm, Sl, **kw))              # ... and not the L-tap one
