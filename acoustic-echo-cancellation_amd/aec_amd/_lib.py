@@ -30,6 +30,7 @@ EXPORTS = ('aec_weights_count', 'aec_create', 'aec_set_weights', 'aec_set_erb', 
            'aec_prepare', 'aec_prepare_siglens', 'aec_process_prepared',
            'aec_stream_open', 'aec_stream_reset', 'aec_stream_step', 'aec_stream_push',
            'aec_stream_open_rescue', 'aec_stream_rescue_counts',
+           'aec_stream_open_stereo', 'aec_stream_step_stereo', 'aec_stream_push_stereo', 'aec_stream_state',
            'aec_delay_estimate', 'aec_delay_apply', 'aec_drift_estimate', 'aec_drift_apply',
            'aec_delay_track_open', 'aec_delay_track_reset', 'aec_delay_track_push',
            'aec_drift_track_open', 'aec_drift_track_reset', 'aec_drift_track_push',
@@ -139,6 +140,16 @@ def load():
         lib.aec_stream_open_rescue.restype = ctypes.c_int
         lib.aec_stream_rescue_counts.argtypes = [P, P, P]
         lib.aec_stream_rescue_counts.restype = ctypes.c_int
+    if LIB_PATH == _DEFAULT_LIB or hasattr(lib, 'aec_stream_open_stereo'):   # absent from an older A/B build
+        lib.aec_stream_open_stereo.argtypes = [P, ctypes.c_int32]
+        lib.aec_stream_open_stereo.restype = ctypes.c_int
+        lib.aec_stream_step_stereo.argtypes = [P, P, P, P, ctypes.c_int64, ctypes.c_int64, P, ctypes.c_int64, P]
+        lib.aec_stream_step_stereo.restype = ctypes.c_int
+        lib.aec_stream_push_stereo.argtypes = [P, P, P, P, ctypes.c_int64, ctypes.c_int64, P, ctypes.c_int64, P,
+                                               ctypes.c_int32, P]
+        lib.aec_stream_push_stereo.restype = ctypes.c_int
+        lib.aec_stream_state.argtypes = [P, P, P, P]
+        lib.aec_stream_state.restype = ctypes.c_int
     if LIB_PATH == _DEFAULT_LIB or hasattr(lib, 'aec_delay_estimate'):   # absent from an older A/B build
         lib.aec_delay_estimate.argtypes = [P, P, P, P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, P, P, P]
         lib.aec_delay_estimate.restype = ctypes.c_int
@@ -370,6 +381,28 @@ class Handle:
     def stream_rescue_counts(self, counts_ptr, stream):
         """counts_ptr: device [B] int64, the copies of every stream since open / reset"""
         check(self.lib.aec_stream_rescue_counts(self.h, counts_ptr, stream), self.h, 'aec_stream_rescue_counts')
+
+    def stream_open_stereo(self, B):
+        """Streams of a stereo handle (aec_stream_open_stereo)."""
+        check(self.lib.aec_stream_open_stereo(self.h, int(B)), self.h, 'aec_stream_open_stereo')
+
+    def stream_step_stereo(self, mic_ptr, ref_l_ptr, ref_r_ptr, ld_mic, ld_ref, out_ptr, ld_out, stream):
+        """ref_l_ptr, ref_r_ptr: the channels' rows, both ld_ref floats apart"""
+        check(self.lib.aec_stream_step_stereo(self.h, mic_ptr, ref_l_ptr, ref_r_ptr, int(ld_mic), int(ld_ref), out_ptr,
+                                              int(ld_out), stream), self.h, 'aec_stream_step_stereo')
+
+    def stream_push_stereo(self, mic_ptr, ref_l_ptr, ref_r_ptr, ld_mic, ld_ref, out_ptr, ld_out, hops_ptr, max_hops, stream):
+        """hops_ptr: device [B] int32 hop counts, or None (every stream advances max_hops)"""
+        check(self.lib.aec_stream_push_stereo(self.h, mic_ptr, ref_l_ptr, ref_r_ptr, int(ld_mic), int(ld_ref), out_ptr,
+                                              int(ld_out), hops_ptr, int(max_hops), stream), self.h,
+              'aec_stream_push_stereo')
+
+    def stream_state(self):
+        """(device pointer, floats per stream, streams) of the open streaming state (aec_stream_state)"""
+        p, stride, B = ctypes.c_void_p(0), ctypes.c_int64(0), ctypes.c_int32(0)
+        check(self.lib.aec_stream_state(self.h, ctypes.byref(p), ctypes.byref(stride), ctypes.byref(B)), self.h,
+              'aec_stream_state')
+        return int(p.value), int(stride.value), int(B.value)
 
     def stream_reset(self, b, stream):
         check(self.lib.aec_stream_reset(self.h, int(b), stream), self.h, 'aec_stream_reset')

@@ -396,7 +396,20 @@ class Little_net(nn.Module):
         if torch.is_grad_enabled() and self.training:
             raise NotImplementedError('streaming is inference-only: use net.eval() and torch.no_grad()')
         if self.stereo:
-            raise NotImplementedError('a stereo far end runs on the batch path only (forward / forward_ragged)')
+            raise NotImplementedError('a stereo far end streams two channels: stream_open_stereo opens its streams')
+        self._stream_open(B, erb, device, False)
+
+    def stream_open_stereo(self, B, erb, device=None):
+        """``stream_open`` for a stereo net (``nlms['stereo']``; aec_stream_open_stereo):
+        afterwards ``stream_step_stereo`` / ``stream_push_stereo`` advance the B
+        streams, ``stream_reset`` serves them as any other."""
+        if torch.is_grad_enabled() and self.training:
+            raise NotImplementedError('streaming is inference-only: use net.eval() and torch.no_grad()')
+        if not self.stereo:
+            raise RuntimeError("this net takes one far-end channel (nlms['stereo'] is not set): stream_open opens its streams")
+        self._stream_open(B, erb, device, True)
+
+    def _stream_open(self, B, erb, device, stereo):
         device = torch.device(device or 'cuda')
         if device.type != 'cuda':
             raise RuntimeError(f'Little_net (gfx950) streams live on a HIP device, got {device}')
@@ -404,14 +417,26 @@ class Little_net(nn.Module):
             raise ValueError(f'erb must be [257, 32], got {tuple(erb.shape)}')
         h, idx = self._handle(device)
         self._sync_erb(h, idx, erb)
-        if h.rescue:
+        if stereo:
+            h.stream_open_stereo(B)
+        elif h.rescue:
             h.stream_open_rescue(B)
         else:
             h.stream_open(B)
         self._stream = (h, torch.device('cuda', idx), int(B))
         self._stream_rescue = bool(h.rescue)
+        self._stream_stereo = bool(stereo)
 
-    def _stream_state(self):
+    def _stream_state(self, stereo=False):
+        st = getattr(self, '_stream', None)
+        if st is None:
+            raise RuntimeError('call stream_open_stereo first' if stereo else 'call stream_open first')
+        if bool(getattr(self, '_stream_stereo', False)) != stereo:
+            raise RuntimeError('the open streams take one far-end channel: stream_step / stream_push advance them' if stereo
+                               else 'the open streams are stereo: stream_step_stereo / stream_push_stereo advance them')
+        return st
+
+    def _stream_any(self):
         st = getattr(self, '_stream', None)
         if st is None:
             raise RuntimeError('call stream_open first')
@@ -419,7 +444,7 @@ class Little_net(nn.Module):
 
     def stream_reset(self, b=-1):
         """Zero stream b's state (b = -1: every stream) for a new utterance."""
-        h, device, _ = self._stream_state()
+        h, device, _ = self._stream_any()
         h.stream_reset(b, torch.cuda.current_stream(device).cuda_stream)
 
     def stream_rescue_counts(self):
@@ -427,7 +452,7 @@ class Little_net(nn.Module):
         ``stream_open`` / ``stream_reset``: int64 [B] on the streams' device, written
         in stream order (nothing synchronises).  A count that moves says that
         stream's echo path changed."""
-        h, device, B = self._stream_state()
+        h, device, B = self._stream_any()
         if not getattr(self, '_stream_rescue', False):
             raise RuntimeError("the open streams have no canceller rescue (nlms['rescue'])")
         counts = torch.empty(B, device=device, dtype=torch.int64)
@@ -492,6 +517,56 @@ class Little_net(nn.Module):
             h.stream_push(mic.data_ptr(), ref.data_ptr(), mic.stride(0), out.data_ptr(), HOP * K,
                           hops.data_ptr() if hops is not None else None, K,
                           torch.cuda.current_stream(device).cuda_stream)
+        return out
+
+    def _stereo_packet(self, mic, ref, what):
+        """mic [B, W], ref [B, 2, W] as the stereo calls pass them: float32, unit sample
+        stride; ref is handed over as it lies (a contiguous [B, 2, W] needs no copy)"""
+        h, device, B = self._stream_state(stereo=True)
+        if mic.device != device or mic.dim() != 2 or mic.shape[0] != B or mic.shape[1] < HOP:
+            raise ValueError(f'mic {what} must be [{B}, >= 256] on {device}')
+        if ref.device != device or ref.dim() != 3 or ref.shape[0] != B or ref.shape[1] != 2 or ref.shape[2] != mic.shape[1]:
+            raise ValueError(f'ref {what} must be [{B}, 2, {mic.shape[1]}] on {device}, got {tuple(ref.shape)}')
+        K = mic.shape[1] // HOP
+        mic = mic.float()
+        ref = ref.float()
+        if mic.stride(1) != 1 or mic.stride(0) < HOP * K:
+            mic = mic.contiguous()
+        if ref.stride(2) != 1 or ref.stride(0) < HOP * K:
+            ref = ref.contiguous()
+        return h, device, B, K, mic, ref
+
+    def stream_step_stereo(self, mic, ref):
+        """mic [B, 256], ref [B, 2, 256] float32 (hop k of every stream: left and right
+        far-end channel, each already normalised as the batch call normalises it — see
+        aec_stream_step_stereo) -> output hop k-1 [B, 256]."""
+        h, device, B, _, mic, ref = self._stereo_packet(mic, ref, 'hops')
+        self._handle(device)            # weights may have changed
+        out = torch.empty(B, HOP, device=device, dtype=torch.float32)
+        with torch.cuda.device(device):
+            h.stream_step_stereo(mic.data_ptr(), ref.data_ptr(), ref.data_ptr() + 4 * ref.stride(1), mic.stride(0),
+                                 ref.stride(0), out.data_ptr(), HOP, torch.cuda.current_stream(device).cuda_stream)
+        return out
+
+    def stream_push_stereo(self, mic, ref, hops=None):
+        """``stream_push`` for stereo streams (aec_stream_push_stereo): mic [B, W], ref
+        [B, 2, W] float32, K = W // 256 hops per row back to back; ``hops`` and the
+        result [B, 256 K] exactly as for ``stream_push`` (zeros where counts leave rows
+        unwritten; int32 counts on the device are not synchronised)."""
+        h, device, B, K, mic, ref = self._stereo_packet(mic, ref, 'packets')
+        if hops is not None:
+            if not torch.is_tensor(hops):
+                hops = torch.tensor([int(v) for v in hops], dtype=torch.int32).to(device)
+            if hops.device != device or hops.dtype != torch.int32 or hops.dim() != 1 or hops.shape[0] != B:
+                raise ValueError(f'hops must be an int32 tensor [{B}] on {device}')
+            hops = hops.contiguous()
+        self._handle(device)            # weights may have changed
+        alloc = torch.empty if hops is None else torch.zeros
+        out = alloc(B, HOP * K, device=device, dtype=torch.float32)
+        with torch.cuda.device(device):
+            h.stream_push_stereo(mic.data_ptr(), ref.data_ptr(), ref.data_ptr() + 4 * ref.stride(1), mic.stride(0),
+                                 ref.stride(0), out.data_ptr(), HOP * K, hops.data_ptr() if hops is not None else None, K,
+                                 torch.cuda.current_stream(device).cuda_stream)
         return out
 
     def debug_intermediate(self, what, B, T, device=None):

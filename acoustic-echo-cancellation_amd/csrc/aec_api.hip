@@ -131,6 +131,7 @@ struct aec_handle {
     int32_t stream_B = 0;
     int64_t stream_stride = 0;
     bool stream_rescue = false;  // the state is a rescue stream's (aec_stream_open_rescue): shadow rows, copy counter
+    bool stream_stereo = false;  // the state is a stereo stream's (aec_stream_open_stereo): stereo_stream_rows' layout
     // streaming delay tracker (aec_delay_track_*): per-stream state [track_B][track_stride]
     float* d_track = nullptr;
     float* d_drift_tab = nullptr;   // the resampler's interpolation table (aec_drift.h build_drift_table)
@@ -288,6 +289,7 @@ const char* aec_build_info(void) {
                                     " canceller_rescue=kalman:1-" + std::to_string(aec::kRescueMaxTaps) +
                                     " stream_rescue=kalman:1-" + std::to_string(aec::kRescueMaxTaps) +
                                     " canceller_stereo=kalman:1-" + std::to_string(aec::kStereoMaxTaps) +
+                                    " stream_stereo=kalman:1-" + std::to_string(aec::kStereoMaxTaps) +
                                     " mode_knobs=" + aec::kModeKnobs;
     return info.c_str();
 }
@@ -574,7 +576,8 @@ aec_status aec_process_siglens(aec_handle* h, const float* mic, const float* ref
 }
 
 static const char kStereoOnly[] = "a stereo handle (aec_set_canceller_stereo) takes its batches through aec_process_stereo";
-static const char kStereoNoStream[] = "a stereo handle (aec_set_canceller_stereo) has no streaming state: aec_process_stereo is its only path";
+static const char kStereoNoStream[] = "a stereo handle (aec_set_canceller_stereo) has no mono streaming state: aec_process_stereo is its batch path and aec_stream_open_stereo opens its streams";
+static const char kStereoStreamOnly[] = "the open state is a stereo stream's (aec_stream_open_stereo): aec_stream_step_stereo / aec_stream_push_stereo advance it";
 
 aec_status aec_process_stereo(aec_handle* h, const float* mic, const float* ref_l, const float* ref_r, const float* near,
                               const int64_t* lengths, int32_t B, int64_t ld, float* out, int64_t ld_out, float* loss,
@@ -919,16 +922,20 @@ aec_status aec_erb_tables_check(const float* erb, const float* mags, const float
 
 // B streams' state for the handle's canceller (rescue: with the shadow's rows, which like the
 // counter start at zero): zeroed, the Kalman covariances at p0, a previous state replaced
-static aec_status stream_open_state(aec_handle* h, int32_t B, bool rescue) {
-    const int64_t stride = stream_state_floats(h->cfg.nlms_taps, h->canc.kind, rescue);
+static aec_status stream_open_state(aec_handle* h, int32_t B, bool rescue, bool stereo = false) {
+    // a stereo stream: the block of a plain Kalman stream with twice the taps (stereo_stream_rows)
+    const int taps = stereo ? 2 * h->cfg.nlms_taps : h->cfg.nlms_taps;
+    const int64_t stride = stream_state_floats(taps, h->canc.kind, rescue);
     h->stream_rescue = false;
+    h->stream_stereo = false;
     const aec_status s = state_open(h, h->d_state, h->stream_B, B, stride);
     if (s != AEC_OK) return s;
     h->stream_stride = stride;
     h->stream_rescue = rescue;
+    h->stream_stereo = stereo;
     if (h->canc.kind == kCancellerKalman) {
         h->stream_B = 0;                  // no stream to step until the covariances are in place
-        HIP_TRY(h, launch_stream_cov_fill(h->d_state, stride, 0, B, h->cfg.nlms_taps, h->canc.p0, nullptr));
+        HIP_TRY(h, launch_stream_cov_fill(h->d_state, stride, 0, B, taps, h->canc.p0, nullptr));
         HIP_TRY(h, hipStreamSynchronize(nullptr));
         h->stream_B = B;
     }
@@ -953,6 +960,24 @@ aec_status aec_stream_open_rescue(aec_handle* h, int32_t B) {
     return stream_open_state(h, B, true);
 }
 
+aec_status aec_stream_open_stereo(aec_handle* h, int32_t B) {
+    if (!h) return AEC_ERR_INVALID_ARG;
+    if (!h->stereo) return fail(h, AEC_ERR_INVALID_ARG, "the stereo far end is not on for this handle (aec_set_canceller_stereo)");
+    if (B < 1) return fail(h, AEC_ERR_INVALID_ARG, "stream count must be >= 1");
+    AEC_ON_DEVICE(h);
+    return stream_open_state(h, B, false, true);
+}
+
+aec_status aec_stream_state(aec_handle* h, float** state, int64_t* stride, int32_t* B) {
+    if (!h) return AEC_ERR_INVALID_ARG;
+    if (!h->d_state) return fail(h, AEC_ERR_INVALID_ARG, "no open streaming state");
+    if (!state || !stride) return fail(h, AEC_ERR_INVALID_ARG, "null state / stride");
+    *state = h->d_state;
+    *stride = h->stream_stride;
+    if (B) *B = h->stream_B;
+    return AEC_OK;
+}
+
 aec_status aec_stream_rescue_counts(aec_handle* h, int64_t* counts, void* stream) {
     if (!h) return AEC_ERR_INVALID_ARG;
     if (!h->d_state || !h->stream_rescue) return fail(h, AEC_ERR_INVALID_ARG, "aec_stream_open_rescue first");
@@ -967,8 +992,9 @@ aec_status aec_stream_reset(aec_handle* h, int32_t b, void* stream) {
     const aec_status s = state_reset(h, h->d_state, h->stream_B, h->stream_stride, b, "aec_stream_open first", stream);
     if (s != AEC_OK || h->canc.kind != kCancellerKalman) return s;
     AEC_ON_DEVICE(h);
-    HIP_TRY(h, launch_stream_cov_fill(h->d_state, h->stream_stride, b < 0 ? 0 : b, b < 0 ? h->stream_B : 1, h->cfg.nlms_taps,
-                                      h->canc.p0, reinterpret_cast<hipStream_t>(stream)));
+    HIP_TRY(h, launch_stream_cov_fill(h->d_state, h->stream_stride, b < 0 ? 0 : b, b < 0 ? h->stream_B : 1,
+                                      h->stream_stereo ? 2 * h->cfg.nlms_taps : h->cfg.nlms_taps, h->canc.p0,
+                                      reinterpret_cast<hipStream_t>(stream)));
     return AEC_OK;
 }
 
@@ -976,6 +1002,7 @@ aec_status aec_stream_step(aec_handle* h, const float* mic, const float* ref, in
                            int64_t ld_out, void* stream) {
     if (!h) return AEC_ERR_INVALID_ARG;
     if (!h->d_state) return fail(h, AEC_ERR_INVALID_ARG, "aec_stream_open first");
+    if (h->stream_stereo) return fail(h, AEC_ERR_INVALID_ARG, kStereoStreamOnly);
     if (!h->have_w || !h->have_erb) return fail(h, AEC_ERR_INVALID_ARG, "weights / erb not set");
     if (!mic || !ref || !out) return fail(h, AEC_ERR_INVALID_ARG, "null mic / ref / out");
     if (ld_in < 256 || ld_out < 256) return fail(h, AEC_ERR_INVALID_ARG, "ld_in / ld_out must be >= 256");
@@ -998,6 +1025,7 @@ aec_status aec_stream_push(aec_handle* h, const float* mic, const float* ref, in
                            int64_t ld_out, const int32_t* hops, int32_t max_hops, void* stream) {
     if (!h) return AEC_ERR_INVALID_ARG;
     if (!h->d_state) return fail(h, AEC_ERR_INVALID_ARG, "aec_stream_open first");
+    if (h->stream_stereo) return fail(h, AEC_ERR_INVALID_ARG, kStereoStreamOnly);
     if (!h->have_w || !h->have_erb) return fail(h, AEC_ERR_INVALID_ARG, "weights / erb not set");
     if (!mic || !ref || !out) return fail(h, AEC_ERR_INVALID_ARG, "null mic / ref / out");
     const Check c = check_stream_push(max_hops, ld_in, ld_out);
@@ -1022,6 +1050,44 @@ aec_status aec_stream_push(aec_handle* h, const float* mic, const float* ref, in
     }
     HIP_TRY(h, launch_stream_push(a, h->stream_B, reinterpret_cast<hipStream_t>(stream)));
     return AEC_OK;
+}
+
+// The stereo streams (kernels in aec_stream_stereo.hip).  hops == nullptr and
+// max_hops == 1 is the step.
+static aec_status stream_stereo_call(aec_handle* h, const float* mic, const float* ref_l, const float* ref_r, int64_t ld_mic,
+                                     int64_t ld_ref, float* out, int64_t ld_out, const int32_t* hops, int32_t max_hops,
+                                     bool step, void* stream) {
+    if (!h) return AEC_ERR_INVALID_ARG;
+    if (!h->d_state || !h->stream_stereo) return fail(h, AEC_ERR_INVALID_ARG, "aec_stream_open_stereo first");
+    if (!h->have_w || !h->have_erb) return fail(h, AEC_ERR_INVALID_ARG, "weights / erb not set");
+    if (!mic || !ref_l || !ref_r || !out) return fail(h, AEC_ERR_INVALID_ARG, "null mic / ref_l / ref_r / out");
+    Check c = check_stream_push(max_hops, ld_mic, ld_out);
+    if (c.status == AEC_OK) c = check_stream_push(max_hops, ld_ref, ld_out);
+    if (c.status != AEC_OK) return fail(h, c.status, std::string(c.why) + " (ld_in: ld_mic and ld_ref)");
+    AEC_ON_DEVICE(h);
+    StreamStereoArgs a{};
+    a.p.s.mic = mic; a.p.s.ref = ref_l; a.p.s.ld_in = ld_mic; a.p.s.out = out; a.p.s.ld_out = ld_out;
+    a.ref_r = ref_r; a.ld_ref = ld_ref;
+    a.p.s.state = h->d_state; a.p.s.state_stride = h->stream_stride;
+    a.p.s.w = h->d_w; a.p.s.tables = reinterpret_cast<const float*>(h->d_tab);
+    a.p.s.sched = h->d_sched; a.p.s.sched_len = h->sched_len; a.p.s.bintab = h->d_bintab;
+    a.p.s.c = h->canceller();
+    a.p.hops = hops; a.p.max_hops = max_hops;
+    // one hop for every stream is the step: the same result from the kernel without the hop loop
+    if (step || (!hops && max_hops == 1)) HIP_TRY(h, launch_stream_step_stereo(a, h->stream_B, reinterpret_cast<hipStream_t>(stream)));
+    else HIP_TRY(h, launch_stream_push_stereo(a, h->stream_B, reinterpret_cast<hipStream_t>(stream)));
+    return AEC_OK;
+}
+
+aec_status aec_stream_step_stereo(aec_handle* h, const float* mic, const float* ref_l, const float* ref_r, int64_t ld_mic,
+                                  int64_t ld_ref, float* out, int64_t ld_out, void* stream) {
+    return stream_stereo_call(h, mic, ref_l, ref_r, ld_mic, ld_ref, out, ld_out, nullptr, 1, true, stream);
+}
+
+aec_status aec_stream_push_stereo(aec_handle* h, const float* mic, const float* ref_l, const float* ref_r, int64_t ld_mic,
+                                  int64_t ld_ref, float* out, int64_t ld_out, const int32_t* hops, int32_t max_hops,
+                                  void* stream) {
+    return stream_stereo_call(h, mic, ref_l, ref_r, ld_mic, ld_ref, out, ld_out, hops, max_hops, false, stream);
 }
 
 // ---------------------------------------------------------------------------

@@ -99,7 +99,8 @@ inline std::string check_canceller_rescue(int taps, int kind, int on, float mu, 
 // The Kalman canceller for a two-channel far end (aec_set_canceller_stereo): taps
 // per channel, the two channels' histories side by side in one filter with per-tap covariances,
 // which is the 2 taps chain of KalmanHalf<2 taps> with half 0 fed the left channel's rows and
-// half 1 the right's (aec_stereo.hip).  The batch path only.
+// half 1 the right's (aec_stereo.hip); the streams (aec_stream_stereo.hip) run the
+// same chain on one lane (StereoBin, aec_frame.h).
 constexpr int kStereoMaxTaps = 8;      // taps per channel the stereo recursion is instantiated for
 // aec_set_canceller_stereo's argument rules, as check_canceller_rescue states the rescue's.  kind:
 // the handle's selected canceller; rescue: its rescue is on.
@@ -166,6 +167,31 @@ constexpr CancellerRows canceller_rows(int taps, bool kalman, bool rescue = fals
         }
     }
     return r;
+}
+
+// A stereo stream (aec_stream_open_stereo) with `taps` per channel has the block of
+// a plain Kalman stream with 2 taps: canceller_rows(2 taps, true), W[0 .. taps) the left channel's
+// and W[taps .. 2 taps) the right's, the covariance rows likewise.  Its 2 taps - 1 history rows
+// hold R_L[t-1 .. t-taps+1], then R_R[t-1 .. t-taps+1], and one row is spare.  The NLMS power row,
+// which the Kalman canceller never reads, keeps the right channel's previous input hop in its
+// first 256 floats (the state prefix has room for two hops only).
+struct StereoStreamRows {
+    int hist_l = 0;     // first of `nhist` = taps - 1 rows
+    int hist_r = 0;     // first of `nhist` rows
+    int nhist = 0;
+    int spare = 0;      // never read or written
+    int prev_r = 0;     // the right channel's previous hop: floats [0, 256) of this row
+};
+constexpr StereoStreamRows stereo_stream_rows(int taps) {
+    StereoStreamRows s;
+    if (taps <= 0) return s;
+    const CancellerRows r = canceller_rows(2 * taps, true);
+    s.nhist = taps - 1;
+    s.hist_l = r.hist;
+    s.hist_r = r.hist + s.nhist;
+    s.spare = s.hist_r + s.nhist;
+    s.prev_r = r.power;
+    return s;
 }
 
 // --------------------------------------------------------------------------

@@ -337,6 +337,58 @@ __device__ __forceinline__ void bin_store(const BIN& nb, float2* nst, int k) {
     }
 }
 
+// One lane's Kalman canceller for a two-channel far end, L taps per channel:
+// KalmanBin<2L> whose slots [0, L) hold the left channel's history R_L[t .. t-L+1] and slots
+// [L, 2L) the right's.  KalmanBin::step shifts the whole chain by one slot, so slot L would take
+// the left channel's oldest entry, which has just left its history: that entry is replaced by
+// R_R[t] before the shift (hist's own expressions), and the shift carries it into slot L while
+// slots [L, 2L - 1) move on by one.  Everything after the shift is KalmanBin<2L>::step itself,
+// whose two partial chains are then the two channels (H = L), the sums KalmanHalf<2L> forms on
+// two lanes in aec_stereo.hip.
+template <int L>
+struct StereoBin : KalmanBin<2 * L> {
+    static constexpr int kChanTaps = L;
+    __device__ __forceinline__ float2 step(float2 d, float2 rl, float2 rr, float a, float beta, float delta) {
+        this->hist(L - 1, rr);
+        return KalmanBin<2 * L>::step(d, rl, a, beta, delta);
+    }
+};
+
+// bin_load / bin_store for bin slot k of a stereo stream's state (stereo_stream_rows' history
+// rows; W, covariances and psi where canceller_rows(2L, true) puts them)
+template <int L>
+__device__ __forceinline__ void stereo_bin_load(StereoBin<L>& nb, const float2* nst, int k, float p0) {
+    constexpr CancellerRows R = canceller_rows(2 * L, true);
+    constexpr StereoStreamRows S = stereo_stream_rows(L);
+    nb.reset(k == 0, p0);
+#pragma unroll
+    for (int l = 0; l < 2 * L; ++l) nb.w[l] = nst[(R.w + l) * kCancellerRow + k];
+#pragma unroll
+    for (int l = 0; l < S.nhist; ++l) {
+        nb.hist(l, nst[(S.hist_l + l) * kCancellerRow + k]);
+        nb.hist(L + l, nst[(S.hist_r + l) * kCancellerRow + k]);
+    }
+#pragma unroll
+    for (int l = 0; l < 2 * L; ++l) nb.pp[l] = nst[(R.cov + l) * kCancellerRow + k];
+    nb.p = nst[R.psi * kCancellerRow + k];
+}
+template <int L>
+__device__ __forceinline__ void stereo_bin_store(const StereoBin<L>& nb, float2* nst, int k) {
+    constexpr CancellerRows R = canceller_rows(2 * L, true);
+    constexpr StereoStreamRows S = stereo_stream_rows(L);
+    auto raw = [&](int l) { return make_float2(nb.p1[l], nb.dual ? nb.p4[l] : -nb.p2[l]); };
+#pragma unroll
+    for (int l = 0; l < 2 * L; ++l) nst[(R.w + l) * kCancellerRow + k] = nb.w[l];
+#pragma unroll
+    for (int l = 0; l < S.nhist; ++l) {
+        nst[(S.hist_l + l) * kCancellerRow + k] = raw(l);
+        nst[(S.hist_r + l) * kCancellerRow + k] = raw(L + l);
+    }
+#pragma unroll
+    for (int l = 0; l < 2 * L; ++l) nst[(R.cov + l) * kCancellerRow + k] = nb.pp[l];
+    nst[R.psi * kCancellerRow + k] = nb.p;
+}
+
 __device__ __forceinline__ void mags_to_scr(float* scr, int lb, int sw, const float2 (&xa)[8], const float2 (&xb)[8],
                                             float2 x128) {
 #pragma unroll

@@ -141,6 +141,16 @@ using StreamStepArgsT = std::conditional_t<RESCUE, StreamStepRescueArgs, StreamS
 template <bool RESCUE>
 using StreamPushArgsT = std::conditional_t<RESCUE, StreamPushRescueArgs, StreamPushArgs>;
 
+// The argument block of the stereo streams (aec_stream_stereo.hip): the plain push
+// block (p.s.mic with p.s.ld_in the mic's rows, p.s.ref the LEFT far-end channel, p.s.c.taps the
+// taps per channel) with the right channel behind it; both channels' rows are ld_ref apart
+struct StreamStereoArgs {
+    StreamPushArgs p;
+    const float* ref_r;
+    int64_t ld_ref;
+};
+static_assert(std::is_trivially_copyable<StreamStereoArgs>::value, "kernel argument blocks");
+
 // dynamic LDS bytes (must match the carve in the kernels)
 inline size_t analysis_smem_bytes(int sched_len) {
     return (size_t)sched_len * 16 * 16 + 32 * 8 + (258 * 2 + 256 * 2 + 512 + (size_t)kFPB * kGroupFloats) * 4;
@@ -224,6 +234,12 @@ hipError_t launch_stream_push_long(const StreamPushArgs& a, int B, hipStream_t s
 hipError_t launch_stream_step_rescue(const StreamStepArgs& a, const CancellerRescue& r, int B, hipStream_t st);
 hipError_t launch_stream_push_rescue(const StreamPushArgs& a, const CancellerRescue& r, int B, hipStream_t st);
 hipError_t launch_stream_rescue_counts(const float* state, int64_t stride, int B, int64_t* counts, hipStream_t st);
+// The Kalman canceller for a two-channel far end, 1..kStereoMaxTaps taps per channel
+// (aec_stream_stereo.hip): kernels of their own over the same helpers, on a state with the layout
+// of a plain Kalman stream of twice the taps (stereo_stream_rows).  The step ignores a.p.hops and
+// a.p.max_hops: one hop for every stream.
+hipError_t launch_stream_step_stereo(const StreamStereoArgs& a, int B, hipStream_t st);
+hipError_t launch_stream_push_stereo(const StreamStereoArgs& a, int B, hipStream_t st);
 // K3+K4 fused (aec_gru_synth.hip): GRU + head + synthesis of the NLMS error spectrum, one stream per
 // block or two (Plan::gru_one, aec_host.h)
 hipError_t launch_gru_synth(const GruArgs& g, const SynthArgs& y, int B, bool one_per_block, hipStream_t st);

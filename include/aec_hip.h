@@ -137,8 +137,8 @@ aec_status aec_set_canceller_rescue(aec_handle* h, int32_t on, float mu, float g
  * handle takes its batches through aec_process_stereo alone, on the K2 / per-stream
  * recursion / mic_erb kernels at every batch size: aec_process, aec_process_siglens,
  * aec_prepare*, aec_process_prepared, aec_stream_open and aec_stream_open_rescue
- * return AEC_ERR_UNSUPPORTED.  on = 0 switches it off, as does every later
- * successful aec_set_canceller.
+ * return AEC_ERR_UNSUPPORTED.  Its streams are aec_stream_open_stereo's (below).
+ * on = 0 switches it off, as does every later successful aec_set_canceller.
  * AEC_ERR_INVALID_ARG: the Kalman canceller is not selected, or a streaming state is
  * open.  AEC_ERR_UNSUPPORTED: nlms_taps > 8, or the canceller rescue is on (and
  * aec_set_canceller_rescue(on != 0) on a stereo handle returns AEC_ERR_UNSUPPORTED). */
@@ -281,6 +281,49 @@ aec_status aec_stream_push(aec_handle* h, const float* mic, const float* ref, in
  * or counts null. */
 aec_status aec_stream_open_rescue(aec_handle* h, int32_t B);
 aec_status aec_stream_rescue_counts(aec_handle* h, int64_t* counts, void* stream);
+
+/* Streams of a stereo handle (aec_set_canceller_stereo): the
+ * two-channel Kalman canceller per hop, nlms_taps (1..8) taps per channel.  Streamed
+ * hop by hop or in packets, with mic, left and right each normalised as
+ * aec_process_stereo normalises them (x - mean(x)/std(x) over the utterance, zeros
+ * past its end), a stream reproduces aec_process_stereo's out row bit for bit.
+ *   aec_stream_open_stereo(h, B)   B concurrent streams; state zeroed, P = p0; a
+ *        previous state of any kind is replaced.  The state has the size and rows
+ *        of a plain Kalman stream with 2 nlms_taps taps.
+ *   aec_stream_step_stereo(h, mic, ref_l, ref_r, ld_mic, ld_ref, out, ld_out, st)
+ *        mic: device [B, ld_mic]; ref_l, ref_r: device, row b of either channel at
+ *        b * ld_ref floats from its pointer: hop k of every stream (256 samples).
+ *        The two channels share ld_ref, so a contiguous [B, 2, W] tensor passes
+ *        without a copy as ref_l = p, ref_r = p + W, ld_ref = 2 W.  out as in
+ *        aec_stream_step.
+ *   aec_stream_push_stereo(h, mic, ref_l, ref_r, ld_mic, ld_ref, out, ld_out, hops,
+ *        max_hops, st)   a packet of hops per stream in one launch; hops, the
+ *        clamp to [0, max_hops], the untouched 0-hop stream and max_hops == 1 with
+ *        hops == NULL exactly as in aec_stream_push; ld_mic, ld_ref and ld_out must
+ *        be >= 256 max_hops.
+ * Step and push mix on one state; aec_stream_reset serves it; while it is open the
+ * setters refuse as for any open stream.  A digitally silent channel (a hard-panned
+ * source) arrives as zeros after the caller's normalisation and the filter runs
+ * finite: that channel's taps stay 0.  (The batch call normalises on the device,
+ * where a constant channel gives 0/0.)
+ * AEC_ERR_INVALID_ARG: aec_stream_open_stereo on a handle without stereo or with
+ * B < 1; the step / push without an open stereo state, or with the argument errors
+ * of aec_stream_push; aec_stream_step / aec_stream_push on an open stereo state
+ * (the text names these entries); aec_stream_rescue_counts on a stereo state. */
+aec_status aec_stream_open_stereo(aec_handle* h, int32_t B);
+aec_status aec_stream_step_stereo(aec_handle* h, const float* mic, const float* ref_l, const float* ref_r,
+                                  int64_t ld_mic, int64_t ld_ref, float* out, int64_t ld_out, void* stream);
+aec_status aec_stream_push_stereo(aec_handle* h, const float* mic, const float* ref_l, const float* ref_r,
+                                  int64_t ld_mic, int64_t ld_ref, float* out, int64_t ld_out,
+                                  const int32_t* hops, int32_t max_hops, void* stream);
+
+/* Tests and debugging: the open streaming state of any kind (aec_stream_open*), for
+ * reading.  *state: DEVICE [*B, *stride] float32, stream b's block at b * *stride
+ * floats, in the layout DESIGN.md 19 / 29 / 32 describe; valid until the next
+ * aec_stream_open* or aec_destroy.  B may be NULL.  Nothing is synchronised: order the
+ * read after the streaming calls yourself.  AEC_ERR_INVALID_ARG: no open state, or a
+ * null state / stride. */
+aec_status aec_stream_state(aec_handle* h, float** state, int64_t* stride, int32_t* B);
 
 /* Far-end bulk delay (no reference counterpart).  The cancellers
  * see nlms_taps <= 16 frames (256 ms) of far-end history; play-out and capture
@@ -586,8 +629,8 @@ const char* aec_last_error(const aec_handle* h);
  * provenance).  "arch=gfx950 ab_knobs=off ... mode_knobs=<names>": ab_knobs=on marks
  * an A/B build (-DAEC_AB_KNOBS) that reads timing-only / work-skipping knobs;
  * canceller_rescue= and stream_rescue= name the canceller and tap range the batch
- * and the streaming rescue are built for, canceller_stereo= those of the stereo
- * far end (taps per channel); mode_knobs lists the environment
+ * and the streaming rescue are built for, canceller_stereo= and stream_stereo= those
+ * of the stereo far end, batch and streaming (taps per channel); mode_knobs lists the environment
  * variables that select tested modes. */
 const char* aec_build_info(void);
 void aec_destroy(aec_handle* h);
