@@ -31,6 +31,12 @@
 #ifndef AEC_SPEC_ST_NT
 #define AEC_SPEC_ST_NT 0   // E-spectrum stores nt (A/B builds only)
 #endif
+#ifndef AEC_K2N_CVAL_SGPR
+#define AEC_K2N_CVAL_SGPR 1   // K2n: normaliser scalars read once per kernel into SGPRs (0: per transform, A/B)
+#endif
+#ifndef AEC_K2N_E_BUF
+#define AEC_K2N_E_BUF 1       // K2n: E rows through raw buffer stores, a descriptor per row (0: guarded global stores, A/B)
+#endif
 
 #include "aec_fft.h"
 #include "aec_frame.h"
@@ -478,6 +484,14 @@ __global__ __launch_bounds__(kNlmsWaves * 64, 1) void nlms_analysis_kernel(NlmsA
         BIN st;
         st.reset(k == 0, p.c.p0);
         float2 dd[kFPB], rr[kFPB];
+#if AEC_K2N_E_BUF
+        // the stream's first E row, provably wave-uniform (the descriptor stays in SGPRs).
+        // readfirstlane returns int: each half goes through uint32_t, or a low half with bit 31
+        // set sign-extends over the high half
+        const uint64_t spec_a = reinterpret_cast<uint64_t>(spec);
+        const uint64_t spec_u = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(spec_a >> 32)) << 32 |
+                                (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)spec_a);
+#endif
         for (int c = 0; c < nch + 2; ++c) {
             TICK_STAMP(0);
             const int c1 = c - 1;
@@ -487,6 +501,18 @@ __global__ __launch_bounds__(kNlmsWaves * 64, 1) void nlms_analysis_kernel(NlmsA
                 // reads again (the unrolled loop stays branch-free)
                 const int64_t t0 = (int64_t)c1 * kFPB;
                 float* eb = sE + (c1 & 1) * kFPB * kNRow;
+#if AEC_K2N_E_BUF
+                // The E rows go through raw buffer stores: a descriptor per row, formed in scalar
+                // registers from the stream's row t0 (base + i rows; 2 KiB of records for a row
+                // that exists, none for a frame past the stream end), and the one lane offset
+                // 8 k.  The store of a frame past the end lies outside its descriptor and the
+                // hardware drops it, so the 16 steps are one basic block: with a guard per store
+                // each step was a block of its own behind a wave-uniform branch, with a 64-bit
+                // address per lane.  (One descriptor per tick with the lane offset 2048 i + 8 k
+                // was measured slower: tools/archive/k2n_e_tick_descriptor.patch.)
+                const int erows = (int)max((int64_t)0, min((int64_t)kFPB, T - t0));    // rows of the chunk that exist
+                const uint64_t ebase = spec_u + (uint64_t)t0 * (kSpecRow * 8);
+#endif
 #pragma unroll
                 for (int i = 0; i < kFPB; ++i) {
                     const float2 e = st.step(dd[i], rr[i], mu, beta, delta);
@@ -502,6 +528,17 @@ __global__ __launch_bounds__(kNlmsWaves * 64, 1) void nlms_analysis_kernel(NlmsA
 #else
                     reinterpret_cast<float2*>(eb + i * kERow)[k] = e;
 #endif
+#if AEC_K2N_E_BUF
+                    typedef uint32_t u2v __attribute__((ext_vector_type(2)));
+                    const __amdgpu_buffer_rsrc_t ers = __builtin_amdgcn_make_buffer_rsrc(
+                        reinterpret_cast<void*>(ebase + (uint64_t)i * (kSpecRow * 8)), (short)0,
+                        __builtin_amdgcn_readfirstlane(i < erows ? kSpecRow * 8 : 0), 0x00020000);
+                    __builtin_amdgcn_raw_buffer_store_b64(u2v{__float_as_uint(e.x), __float_as_uint(e.y)}, ers, k * 8, 0,
+                                                          AEC_SPEC_ST_NT ? 2 : 0);
+                    // the Kalman recursion from 5 taps up has no registers to spare for steps that overlap
+                    // (<5> took scratch): its steps stay in order, as the branches kept them
+                    if constexpr (BIN::kKalman && BIN::kTaps >= 5) __builtin_amdgcn_sched_barrier(0);
+#else
                     if (t0 + i < T) {
 #if AEC_SPEC_ST_NT
                         typedef float f2v __attribute__((ext_vector_type(2)));
@@ -511,6 +548,7 @@ __global__ __launch_bounds__(kNlmsWaves * 64, 1) void nlms_analysis_kernel(NlmsA
                         spec[(t0 + i) * kSpecRow + k] = e;
 #endif
                     }
+#endif
                 }
             }
             if constexpr (BIN::kErbOnNlmsWaves)
@@ -540,6 +578,19 @@ __global__ __launch_bounds__(kNlmsWaves * 64, 1) void nlms_analysis_kernel(NlmsA
     } else {
         wave_prefetch(pf, row_ref, n_ref, 4 * q, lane, al_ref);
     }
+#if AEC_K2N_CVAL_SGPR
+    // The normaliser scalars of this wave's transforms (mic waves: near and mic, ref waves: ref) are
+    // constant for the kernel: read once and made provably wave-uniform, they stay in SGPRs across
+    // nlms_transform's memory clobber.  Read inside the loop each was a vector load and an
+    // s_waitcnt vmcnt(0) at the head of wave_commit: one trip to memory per transform, which on
+    // the mic waves also drained the feature stores just issued.
+    auto uniformf = [](float v) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(v))); };
+    const float cv_main = uniformf(p.cvals[b * 3 + (role == 0 ? 0 : 1)]);
+    const float cv_near = role == 0 && have_near ? uniformf(p.cvals[b * 3 + 2]) : 0.f;
+    auto cval = [&](int s) { return s == 2 ? cv_near : cv_main; };
+#else
+    auto cval = [&](int s) { return p.cvals[b * 3 + s]; };
+#endif
     for (int c = 0; c < nch + 2; ++c) {
         TICK_STAMP(0);
         const int wt = c * kFPB + 4 * q;
@@ -548,7 +599,7 @@ __global__ __launch_bounds__(kNlmsWaves * 64, 1) void nlms_analysis_kernel(NlmsA
         if (role == 0) {
             if (c < nch && !(p.mode & 8)) {
                 if (have_near) {
-                    nlms_transform(wr, scr, pf, p.cvals[b * 3 + 2], n_near, wt, lane, gg, lb, sHann, sTwT, sTw512,
+                    nlms_transform(wr, scr, pf, cval(2), n_near, wt, lane, gg, lb, sHann, sTwT, sTw512,
                                    row_mic, n, wt, al_mic, xa, xb, x128);
                     if (!(p.mode & 2)) {
                         mags_to_scr(scr, lb, sw, xa, xb, x128);
@@ -557,7 +608,7 @@ __global__ __launch_bounds__(kNlmsWaves * 64, 1) void nlms_analysis_kernel(NlmsA
                     }
                 }
                 const bool more = c + 1 < nch;
-                nlms_transform(wr, scr, pf, p.cvals[b * 3 + 0], n, wt, lane, gg, lb, sHann, sTwT, sTw512,
+                nlms_transform(wr, scr, pf, cval(0), n, wt, lane, gg, lb, sHann, sTwT, sTw512,
                                more ? (have_near ? row_near : row_mic) : nullptr, have_near ? n_near : n, wt + kFPB,
                                have_near ? al_near : al_mic, xa, xb, x128);
                 row_to_scr(scr, lb, xa, xb, x128);
@@ -566,7 +617,7 @@ __global__ __launch_bounds__(kNlmsWaves * 64, 1) void nlms_analysis_kernel(NlmsA
         } else {
             const bool erb2 = erb_role == 1 && c >= 2 && !(p.mode & 4);     // mic_erb of chunk c-2 due
             if (c < nch && !(p.mode & 8)) {
-                nlms_transform(wr, scr, pf, p.cvals[b * 3 + 1], n_ref, wt, lane, gg, lb, sHann, sTwT, sTw512,
+                nlms_transform(wr, scr, pf, cval(1), n_ref, wt, lane, gg, lb, sHann, sTwT, sTw512,
                                c + 1 < nch ? row_ref : nullptr, n_ref, wt + kFPB, al_ref, xa, xb, x128);
                 mags_to_scr(scr, lb, sw, xa, xb, x128);
                 wave_fence();

@@ -92,8 +92,25 @@ __device__ __forceinline__ void wave_prefetch(float4 (&pf)[kWavePf], const float
     }
 }
 // Normalise (x - c) inside [0, n) only — the zero padding stays 0 — and stage.
+// The span [(t-1) * 256, (t+4) * 256) lies inside [0, n) for every wave of a
+// stream but those at its two ends: a wave-uniform test (t and n are the
+// wave's; made provably so) takes those past the per-float masks, with the
+// same subtraction on the same operands.
+#ifndef AEC_COMMIT_FAST
+#define AEC_COMMIT_FAST 1   // 0 = always the masked form (A/B)
+#endif
 __device__ __forceinline__ void wave_commit(float* wr, const float4 (&pf)[kWavePf], float c, int n,
                                             int t, int lane) {
+#if AEC_COMMIT_FAST
+    if (__builtin_amdgcn_readfirstlane(t >= 1 && t + kWaveFrames <= (n >> 8))) {      // (t + 4) * kHop <= n
+#pragma unroll
+        for (int u = 0; u < kWavePf; ++u) {
+            const float4 v = pf[u];
+            *reinterpret_cast<float4*>(wr + u * kHopStride + 4 * lane) = make_float4(v.x - c, v.y - c, v.z - c, v.w - c);
+        }
+        return;
+    }
+#endif
     const int base = (t - 1) * kHop + 4 * lane;
 #pragma unroll
     for (int u = 0; u < kWavePf; ++u) {
