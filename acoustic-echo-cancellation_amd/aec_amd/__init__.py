@@ -12,7 +12,7 @@ Public surface (mirrors the reference):
   * ``dccrn.DCCRN(config)`` / ``dccrn2.DCCRN(config)`` scripts/network/dccrn.py:453, dccrn2.py:10 (CRN, eval)
 The compute runs in ``libaec_hip.so`` (C ABI: include/aec_hip.h, include/aec_crn.h).
 """
-from .configs import speech_conf, erb_conf, train_conf, nlms_conf, kalman_conf, kalman_rescue_conf, kalman_stereo_conf, net_conf  # noqa: F401
+from .configs import speech_conf, erb_conf, train_conf, nlms_conf, kalman_conf, kalman_rescue_conf, kalman_stereo_conf, kalman_stereo_rescue_conf, net_conf  # noqa: F401
 from .erb import EquivalentRectangularBandwidth, erb_matrix     # noqa: F401
 from .little_net import Little_net                              # noqa: F401
 from .delay import estimate_delay, align_ref, DelayTracker      # noqa: F401  (far-end bulk delay, DESIGN.md 20, 21)

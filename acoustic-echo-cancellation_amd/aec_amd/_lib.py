@@ -24,7 +24,7 @@ _STATUS = {0: 'AEC_OK', 1: 'AEC_ERR_INVALID_ARG', 2: 'AEC_ERR_OOM', 3: 'AEC_ERR_
 
 # every symbol include/aec_hip.h declares
 EXPORTS = ('aec_weights_count', 'aec_create', 'aec_set_weights', 'aec_set_erb', 'aec_set_canceller', 'aec_set_canceller_rescue',
-           'aec_set_canceller_stereo', 'aec_process_stereo',
+           'aec_set_canceller_stereo', 'aec_set_canceller_stereo_rescue', 'aec_process_stereo',
            'aec_process',
            'aec_process_siglens',
            'aec_prepare', 'aec_prepare_siglens', 'aec_process_prepared',
@@ -112,6 +112,9 @@ def load():
         lib.aec_set_canceller_stereo.restype = ctypes.c_int
         lib.aec_process_stereo.argtypes = [P, P, P, P, P, P, ctypes.c_int32, ctypes.c_int64, P, ctypes.c_int64, P, P]
         lib.aec_process_stereo.restype = ctypes.c_int
+    if LIB_PATH == _DEFAULT_LIB or hasattr(lib, 'aec_set_canceller_stereo_rescue'):   # absent from an older A/B build
+        lib.aec_set_canceller_stereo_rescue.argtypes = [P, ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float]
+        lib.aec_set_canceller_stereo_rescue.restype = ctypes.c_int
     lib.aec_process.argtypes = [P, P, P, P, P, ctypes.c_int32, ctypes.c_int64, P, ctypes.c_int64, P, P]
     lib.aec_process.restype = ctypes.c_int
     lib.aec_process_siglens.argtypes = [P, P, P, P, P, ctypes.c_int32, ctypes.c_int64, P, ctypes.c_int64, P, P]
@@ -301,6 +304,7 @@ class Handle:
         self.device = device
         self.rescue = False                # the Kalman canceller's rescue is on (set_canceller_rescue)
         self.stereo = False                # the far end has two channels (set_canceller_stereo)
+        self.stereo_rescue = False         # the stereo canceller's own rescue is on (set_canceller_stereo_rescue)
 
     def set_weights(self, blob):
         import numpy as np
@@ -320,6 +324,7 @@ class Handle:
         check(self.lib.aec_set_canceller(self.h, int(kind), float(a), float(p0)), self.h, 'aec_set_canceller')
         self.rescue = False                # every successful aec_set_canceller switches the rescue off
         self.stereo = False                # ... and the stereo far end
+        self.stereo_rescue = False         # ... and its rescue
 
     def set_canceller_rescue(self, on, mu=0.3, gamma=0.9, ratio=0.5):
         """The Kalman canceller's rescue from echo-path changes (aec_set_canceller_rescue)."""
@@ -331,6 +336,14 @@ class Handle:
         """The Kalman canceller over a two-channel far end, taps per channel (aec_set_canceller_stereo)."""
         check(self.lib.aec_set_canceller_stereo(self.h, int(bool(on))), self.h, 'aec_set_canceller_stereo')
         self.stereo = bool(on)
+        self.stereo_rescue = False         # every successful aec_set_canceller_stereo switches the stereo rescue off
+
+    def set_canceller_stereo_rescue(self, on, mu=0.3, gamma=0.9, ratio=0.5):
+        """The stereo canceller's rescue from echo-path changes: the shadow filter over both
+        channels' histories (aec_set_canceller_stereo_rescue); batch path only."""
+        check(self.lib.aec_set_canceller_stereo_rescue(self.h, int(bool(on)), float(mu), float(gamma), float(ratio)),
+              self.h, 'aec_set_canceller_stereo_rescue')
+        self.stereo_rescue = bool(on)
 
     def process_stereo(self, mic_ptr, ref_l_ptr, ref_r_ptr, near_ptr, lengths, B, ld, out_ptr, ld_out, loss_ptr, stream):
         """aec_process_stereo: lengths [B], one length per stream shared by the mic and both channels."""

@@ -79,3 +79,8 @@ kalman_rescue_conf = dict(kalman_conf, rescue=True, mu=0.3, gamma=0.9, ratio=0.5
 # aec_set_canceller_stereo): 'taps' counts the taps per channel
 # (1..8), ref is [B, 2, N].  The batch path.
 kalman_stereo_conf = dict(kalman_conf, stereo=True)
+
+# kalman_stereo_conf with the rescue from abrupt echo-path changes (include/aec_hip.h
+# aec_set_canceller_stereo_rescue): kalman_rescue_conf's shadow filter
+# over both channels' histories.  1..8 taps per channel, the batch path.
+kalman_stereo_rescue_conf = dict(kalman_stereo_conf, rescue=True, mu=0.3, gamma=0.9, ratio=0.5)

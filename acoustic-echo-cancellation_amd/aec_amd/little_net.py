@@ -186,14 +186,16 @@ class Little_net(nn.Module):
                 h.set_canceller('kalman', nl.get('a', 0.999), nl.get('p0', 1.0))
             elif kind != 'nlms':
                 raise ValueError(f"nlms['kind'] must be 'nlms' or 'kalman', got {kind!r}")
-            if nl.get('rescue'):
-                if kind != 'kalman':
-                    raise ValueError("nlms['rescue'] belongs to the Kalman canceller (kind='kalman')")
+            if nl.get('rescue') and kind != 'kalman':
+                raise ValueError("nlms['rescue'] belongs to the Kalman canceller (kind='kalman')")
+            if nl.get('rescue') and not nl.get('stereo'):
                 h.set_canceller_rescue(True, nl.get('mu', 0.3), nl.get('gamma', 0.9), nl.get('ratio', 0.5))
             if nl.get('stereo'):
                 if kind != 'kalman':
                     raise ValueError("nlms['stereo'] belongs to the Kalman canceller (kind='kalman')")
                 h.set_canceller_stereo(True)
+                if nl.get('rescue'):           # the stereo canceller's own rescue (kalman_stereo_rescue_conf)
+                    h.set_canceller_stereo_rescue(True, nl.get('mu', 0.3), nl.get('gamma', 0.9), nl.get('ratio', 0.5))
             self._handles[idx] = h
         if not upload:
             return h, idx
@@ -407,6 +409,8 @@ class Little_net(nn.Module):
             raise NotImplementedError('streaming is inference-only: use net.eval() and torch.no_grad()')
         if not self.stereo:
             raise RuntimeError("this net takes one far-end channel (nlms['stereo'] is not set): stream_open opens its streams")
+        if self.nlms.get('rescue'):
+            raise NotImplementedError("the stereo streams have no rescue (nlms['rescue']): the stereo rescue is the batch path's")
         self._stream_open(B, erb, device, True)
 
     def _stream_open(self, B, erb, device, stereo):

@@ -137,6 +137,42 @@ def scene_stereo(n, seed, double_talk=True, pan=((1.0, 0.3), (0.3, 1.0)), return
     return out
 
 
+def scene_stereo_path_change(n, seed, double_talk=True, change_at=None, pan=((1.0, 0.3), (0.3, 1.0)),
+                             return_echo=False):
+    """scene_stereo() with an abrupt change of both echo paths at sample change_at (default
+    n // 2).  Draws, in order: every source as scene_stereo does, h_l1, h_r1, h_l2, h_r2 = rir
+    four times, then near and noise as scene_stereo does; echo = l * h_l1 + r * h_r1 before
+    change_at and l * h_l2 + r * h_r2 from it on, both scaled by the factor that puts the
+    first at -6 dB relative to the downmix level."""
+    from scipy.signal import fftconvolve
+    rng = np.random.default_rng(seed)
+    if change_at is None:
+        change_at = n // 2
+    src = [_ar1(rng, n) * _envelope(rng, n, rate_hz=4.0 if i == 0 else 3.1) for i in range(len(pan))]
+    l = sum(p[0] * s for p, s in zip(pan, src))
+    r = sum(p[1] * s for p, s in zip(pan, src))
+    g = 0.1 / _rms(0.5 * (l + r))
+    l, r = l * g, r * g
+    level = _rms(0.5 * (l + r))
+    h_l1, h_r1, h_l2, h_r2 = rir(rng), rir(rng), rir(rng), rir(rng)
+    e1 = (fftconvolve(l, h_l1) + fftconvolve(r, h_r1))[:n]
+    e2 = (fftconvolve(l, h_l2) + fftconvolve(r, h_r2))[:n]
+    echo = np.where(np.arange(n) < change_at, e1, e2) * ((level * 10 ** (-6 / 20)) / _rms(e1))
+    if double_talk:
+        near = _ar1(rng, n, a=0.7) * _envelope(rng, n, rate_hz=2.5)
+        gate = (np.sin(2 * np.pi * 0.4 * np.arange(n) / SR + rng.uniform(0, 6.28)) > 0.2)
+        near *= gate
+        near *= (level * 10 ** (-3 / 20)) / max(_rms(near), 1e-12)
+    else:
+        near = np.zeros(n)
+    noise = rng.standard_normal(n) * level * 10 ** (-50 / 20)
+    mic = echo + near + noise
+    out = (mic.astype(np.float32), np.stack([l, r]).astype(np.float32), near.astype(np.float32))
+    if return_echo:
+        out = out + (echo.astype(np.float32),)
+    return out
+
+
 def batch(B, n, seed0=0, double_talk=True):
     """[B, n] float32 arrays (mic, ref, near) with per-stream seeds seed0+b."""
     mic = np.empty((B, n), np.float32)

@@ -94,6 +94,9 @@ struct aec_handle {
     size_t rmask_cap = 0;        // floats
     // a two-channel far end (aec_set_canceller_stereo, aec_process_stereo): allocated for a stereo handle only
     int stereo = 0;
+    // the stereo canceller's own rescue (aec_set_canceller_stereo_rescue): a setting beside `rescue`,
+    // which stays the mono one; its copy decisions share d_rmask
+    CancellerRescue srescue;
     double2* d_smom = nullptr;   // [B][3][kMomChunks] moment partials of (left, right, -)
     int64_t smom_cap = 0;        // streams
     float2* d_srows = nullptr;   // [2][srows_cap / 2] rows of the two normalised channels, [B][T][256] each
@@ -290,6 +293,7 @@ const char* aec_build_info(void) {
                                     " stream_rescue=kalman:1-" + std::to_string(aec::kRescueMaxTaps) +
                                     " canceller_stereo=kalman:1-" + std::to_string(aec::kStereoMaxTaps) +
                                     " stream_stereo=kalman:1-" + std::to_string(aec::kStereoMaxTaps) +
+                                    " canceller_stereo_rescue=kalman:1-" + std::to_string(aec::kStereoRescueMaxTaps) +
                                     " mode_knobs=" + aec::kModeKnobs;
     return info.c_str();
 }
@@ -318,6 +322,7 @@ aec_status aec_set_canceller(aec_handle* h, int32_t kind, float a, float p0) {
     h->canc.kind = kind;
     h->rescue.on = 0;
     h->stereo = 0;
+    h->srescue.on = 0;
     return AEC_OK;
 }
 
@@ -328,6 +333,18 @@ aec_status aec_set_canceller_stereo(aec_handle* h, int32_t on) {
                                                    h->d_state != nullptr, &unsupported);
     if (!why.empty()) return fail(h, unsupported ? AEC_ERR_UNSUPPORTED : AEC_ERR_INVALID_ARG, why);
     h->stereo = on != 0;
+    h->srescue.on = 0;
+    return AEC_OK;
+}
+
+aec_status aec_set_canceller_stereo_rescue(aec_handle* h, int32_t on, float mu, float gamma, float ratio) {
+    if (!h) return AEC_ERR_INVALID_ARG;
+    bool unsupported = false;
+    const std::string why = check_canceller_stereo_rescue(h->cfg.nlms_taps, h->canc.kind, h->stereo != 0, on, mu, gamma,
+                                                          ratio, h->d_state != nullptr, &unsupported);
+    if (!why.empty()) return fail(h, unsupported ? AEC_ERR_UNSUPPORTED : AEC_ERR_INVALID_ARG, why);
+    if (on) h->srescue = CancellerRescue{1, mu, gamma, ratio};
+    else h->srescue.on = 0;
     return AEC_OK;
 }
 
@@ -693,7 +710,7 @@ static aec_status process_impl(aec_handle* h, uint64_t token, const float* mic, 
         }
         HIP_TRY(h, launch_moments(ref, ref_r, nullptr, ld, h->d_slen, h->d_smom, 0, B, 2, st));
     }
-    const bool rmask = p.split && h->rescue.on && h->debug;      // the rescue's copy decisions, for aec_debug_copy
+    const bool rmask = p.split && (h->rescue.on || h->srescue.on) && h->debug;      // the rescue's copy decisions, for aec_debug_copy
     if (rmask && (size_t)B * Tmax * 257 > h->rmask_cap) {
         const size_t need = (size_t)B * Tmax * 257;
         s = grow_after_last(h, h->d_rmask, h->rmask_cap, need, need * sizeof(float), true);
@@ -742,7 +759,11 @@ static aec_status process_impl(aec_handle* h, uint64_t token, const float* mic, 
                 HIP_TRY(h, launch_stereo_rows(sa, st));
                 HIP_TRY(h, launch_stereo_ref_erb(h->d_srows, chan_stride, h->d_feats, Tmax, h->d_sched, h->sched_len,
                                                  h->d_items, a.nitems, st));
-                HIP_TRY(h, launch_recursion_stereo(ra, h->d_srows, chan_stride, h->canceller(), st));
+                if (h->srescue.on)
+                    HIP_TRY(h, launch_recursion_stereo_rescue(ra, h->d_srows, chan_stride, h->canceller(), h->srescue,
+                                                              rmask ? h->d_rmask : nullptr, st));
+                else
+                    HIP_TRY(h, launch_recursion_stereo(ra, h->d_srows, chan_stride, h->canceller(), st));
             } else if (h->rescue.on)
                 HIP_TRY(h, launch_recursion_rescue(ra, h->canceller(), h->rescue, rmask ? h->d_rmask : nullptr, st));
             else
@@ -858,8 +879,8 @@ aec_status aec_debug_copy(aec_handle* h, int32_t what, float* dst, size_t n, voi
     if (what < 0 || what > 7) return fail(h, AEC_ERR_INVALID_ARG, "unknown intermediate");
     if (what == 7 && (!h->d_spec || B * T == 0))
         return fail(h, AEC_ERR_INVALID_ARG, "error_spec: a handle with a linear stage (nlms_taps > 0), after aec_process");
-    if (what == 6 && (!h->debug || !h->rescue.on || (size_t)(B * T * 257) > h->rmask_cap || B * T == 0))
-        return fail(h, AEC_ERR_INVALID_ARG, "rescue_mask: aec_set_canceller_rescue and aec_set_debug before aec_process");
+    if (what == 6 && (!h->debug || !(h->rescue.on || h->srescue.on) || (size_t)(B * T * 257) > h->rmask_cap || B * T == 0))
+        return fail(h, AEC_ERR_INVALID_ARG, "rescue_mask: aec_set_canceller_rescue (or aec_set_canceller_stereo_rescue) and aec_set_debug before aec_process");
     if ((what == 3 || what == 4) && !h->debug) return fail(h, AEC_ERR_INVALID_ARG, "enable aec_set_debug before aec_process");
     // ordered after the last call (it may have run on another stream) like any other call
     aec_status s = begin_call(h, st);
@@ -963,6 +984,7 @@ aec_status aec_stream_open_rescue(aec_handle* h, int32_t B) {
 aec_status aec_stream_open_stereo(aec_handle* h, int32_t B) {
     if (!h) return AEC_ERR_INVALID_ARG;
     if (!h->stereo) return fail(h, AEC_ERR_INVALID_ARG, "the stereo far end is not on for this handle (aec_set_canceller_stereo)");
+    if (h->srescue.on) return fail(h, AEC_ERR_UNSUPPORTED, "the stereo streams have no rescue: switch it off first (aec_set_canceller_stereo_rescue)");
     if (B < 1) return fail(h, AEC_ERR_INVALID_ARG, "stream count must be >= 1");
     AEC_ON_DEVICE(h);
     return stream_open_state(h, B, false, true);

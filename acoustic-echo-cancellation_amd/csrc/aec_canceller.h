@@ -120,6 +120,31 @@ inline std::string check_canceller_stereo(int taps, int kind, int on, bool rescu
     return "";
 }
 
+// The stereo canceller's own rescue (aec_set_canceller_stereo_rescue): the shadow
+// FD-NLMS of the mono rescue run over both channels' histories, RescueBin<2 taps> on two lanes
+// (RescueHalf, aec_stereo_rescue.h).  A setting of its own beside CancellerRescue's mono one: the
+// two older setters keep refusing each other, and the handle's mono rescue stays off.
+constexpr int kStereoRescueMaxTaps = 8;    // taps per channel the stereo rescue recursion is instantiated for
+// aec_set_canceller_stereo_rescue's argument rules.  kind: the handle's selected canceller;
+// stereo: its stereo far end is on.  The values are checked only when the call switches it on.
+inline std::string check_canceller_stereo_rescue(int taps, int kind, bool stereo, int on, float mu, float gamma,
+                                                 float ratio, bool stream_open, bool* unsupported) {
+    *unsupported = false;
+    if (kind != kCancellerKalman || !stereo)
+        return "the stereo rescue belongs to a stereo Kalman handle: aec_set_canceller, then aec_set_canceller_stereo first";
+    if (taps < 1 || taps > kStereoRescueMaxTaps) {
+        *unsupported = true;
+        return "the stereo canceller's rescue exists for 1..8 taps per channel";
+    }
+    if (stream_open) return "a streaming state is open: the stereo streams have no rescue";
+    if (on) {
+        if (!(mu >= 0.f && std::isfinite(mu))) return "rescue step size mu must be finite and >= 0";
+        if (!(gamma >= 0.f && gamma < 1.f)) return "rescue smoothing factor gamma must be in [0, 1)";
+        if (!(ratio >= 0.f && std::isfinite(ratio))) return "rescue ratio must be finite and >= 0";
+    }
+    return "";
+}
+
 // --------------------------------------------------------------------------
 // state layout
 // --------------------------------------------------------------------------

@@ -217,6 +217,11 @@ hipError_t launch_stereo_ref_erb(const float2* rows, int64_t chan_stride, float*
                                  int sched_len, const WorkItem* items, int64_t nitems, hipStream_t st);
 hipError_t launch_recursion_stereo(const RecursionArgs& a, const float2* far, int64_t chan_stride, const Canceller& c,
                                    hipStream_t st);
+// The stereo recursion with its rescue on, 1..kStereoRescueMaxTaps taps per channel
+// (aec_stereo_rescue.hip): launch_recursion_stereo's rows in and E rows out, and
+// launch_recursion_rescue's mask (null, or [B][Tmax][257] copy decisions).
+hipError_t launch_recursion_stereo_rescue(const RecursionArgs& a, const float2* far, int64_t chan_stride,
+                                          const Canceller& c, const CancellerRescue& r, float* mask, hipStream_t st);
 hipError_t launch_mic_erb(const float2* spec, float* feats, const int64_t* lens, int64_t Tmax, const float* sched,
                           int sched_len, const WorkItem* items, int64_t nitems, hipStream_t st);
 hipError_t launch_gru(const GruArgs& a, int B, hipStream_t st);

@@ -17,6 +17,10 @@
  *        selects the build-defined linear stage's adaptive filter (no reference
  *        counterpart): the FD-NLMS (default) or the frequency-domain Kalman
  *        filter, in aec_process, aec_process_prepared and aec_stream_step alike.
+ *   aec_set_canceller_rescue / aec_set_canceller_stereo / aec_set_canceller_stereo_rescue
+ *        options of the Kalman filter (no reference counterpart): a shadow filter that
+ *        rescues it from abrupt echo-path changes, a two-channel far end
+ *        (aec_process_stereo), and the two together on the batch path.
  *   aec_debug_copy
  *        exposes the intermediates the reference computes inside forward
  *        (ERB.py:282-307) for parity tests.
@@ -143,6 +147,27 @@ aec_status aec_set_canceller_rescue(aec_handle* h, int32_t on, float mu, float g
  * open.  AEC_ERR_UNSUPPORTED: nlms_taps > 8, or the canceller rescue is on (and
  * aec_set_canceller_rescue(on != 0) on a stereo handle returns AEC_ERR_UNSUPPORTED). */
 aec_status aec_set_canceller_stereo(aec_handle* h, int32_t on);
+
+/* The stereo canceller's own rescue, off unless switched on here, on a
+ * handle with the Kalman canceller and stereo on.  The shadow FD-NLMS and the decision
+ * of aec_set_canceller_rescue, run over the 2 nlms_taps entries of both channels'
+ * histories R_c,l after the stereo step above:
+ *   Es = D - sum_c sum_l Ws[c][l] R_c,l,  Pn = beta Pn + (1-beta) sum_c sum_l |R_c,l|^2,
+ *   Ws[c][l] += mu Es conj(R_c,l) / (Pn + delta),
+ *   qe = gamma qe + (1-gamma) |E|^2,  qs = gamma qs + (1-gamma) |Es|^2,
+ *   if qs < ratio qe:  W[c][l] = Ws[c][l], P[c][l] = p0 for every c, l;  qe = qs
+ * The output stays the stereo filter's E; ratio = 0 never copies (the plain stereo
+ * canceller, bit for bit).  aec_process_stereo then runs the recursion of
+ * csrc/aec_stereo_rescue.hip in place of the plain stereo one; aec_debug_copy(what = 6)
+ * serves its copy decisions.  A setting of its own: aec_set_canceller_rescue and
+ * aec_set_canceller_stereo keep refusing each other as stated above.  on = 0 switches it
+ * off (mu, gamma, ratio are then ignored), as does every later successful
+ * aec_set_canceller and aec_set_canceller_stereo (on or off).  Batch path only:
+ * aec_stream_open_stereo on a handle with it on returns AEC_ERR_UNSUPPORTED.
+ * AEC_ERR_INVALID_ARG: not a Kalman handle with stereo on, a streaming state is open,
+ * or (on != 0) mu negative or not finite, gamma outside [0, 1), ratio negative or not
+ * finite.  AEC_ERR_UNSUPPORTED: nlms_taps > 8. */
+aec_status aec_set_canceller_stereo_rescue(aec_handle* h, int32_t on, float mu, float gamma, float ratio);
 
 aec_status aec_set_weights(aec_handle* h, const float* weights, size_t n_weights);
 aec_status aec_set_erb(aec_handle* h, const float* erb_257xbands);
@@ -309,7 +334,9 @@ aec_status aec_stream_rescue_counts(aec_handle* h, int64_t* counts, void* stream
  * AEC_ERR_INVALID_ARG: aec_stream_open_stereo on a handle without stereo or with
  * B < 1; the step / push without an open stereo state, or with the argument errors
  * of aec_stream_push; aec_stream_step / aec_stream_push on an open stereo state
- * (the text names these entries); aec_stream_rescue_counts on a stereo state. */
+ * (the text names these entries); aec_stream_rescue_counts on a stereo state.
+ * AEC_ERR_UNSUPPORTED: aec_stream_open_stereo on a handle with the stereo rescue on
+ * (aec_set_canceller_stereo_rescue): the stereo streams have no rescue. */
 aec_status aec_stream_open_stereo(aec_handle* h, int32_t B);
 aec_status aec_stream_step_stereo(aec_handle* h, const float* mic, const float* ref_l, const float* ref_r,
                                   int64_t ld_mic, int64_t ld_ref, float* out, int64_t ld_out, void* stream);
@@ -551,7 +578,8 @@ aec_status aec_drift_track_push(aec_handle* h, const float* mic, const float* re
  * what: 0 = mic_erb, 1 = ref_erb, 2 = near_erb, 3 = gru_out (h_t),
  *       4 = mask, 5 = est_erb;
  *       6 = rescue_mask: the canceller rescue's copy decisions of that call
- *       (aec_set_canceller_rescue), dst [B, T_max, 257] float32, 1 = copied;
+ *       (aec_set_canceller_rescue, or aec_set_canceller_stereo_rescue on a stereo
+ *       handle), dst [B, T_max, 257] float32, 1 = copied;
  *       7 = error_spec: the linear stage's output E of that call (nlms_taps > 0; no
  *       aec_set_debug needed), dst [B, T_max, 256] pairs of float32 (re, im), slot 0
  *       the real pair (E[0], E[256]). */
@@ -630,7 +658,8 @@ const char* aec_last_error(const aec_handle* h);
  * an A/B build (-DAEC_AB_KNOBS) that reads timing-only / work-skipping knobs;
  * canceller_rescue= and stream_rescue= name the canceller and tap range the batch
  * and the streaming rescue are built for, canceller_stereo= and stream_stereo= those
- * of the stereo far end, batch and streaming (taps per channel); mode_knobs lists the environment
+ * of the stereo far end, batch and streaming (taps per channel), canceller_stereo_rescue=
+ * those of the stereo rescue (batch); mode_knobs lists the environment
  * variables that select tested modes. */
 const char* aec_build_info(void);
 void aec_destroy(aec_handle* h);
