@@ -11,6 +11,7 @@
 
 #include "aec_canceller.h"
 #include "aec_fft.h"
+#include "aec_gi_map.h"
 
 namespace aec {
 
@@ -559,6 +560,61 @@ __device__ __forceinline__ float gru_gi(const float (&wih)[64], const float* x, 
     }
     const f2v s2 = a0 + a1;
     return gbias + (s2.x + s2.y);
+}
+
+// gru_gi of one wave's two row tiles (gate rows 16 t0 .. 16 t0 + 31) for the 16 frame slots of a
+// tick, on the matrix pipe: v_mfma_f32_16x16x4_f32 is the fmaf chain over its four K indices, so
+// one accumulator tile per chain c_r of gru_gi (r = k % 4), four chained instructions each, gives
+// the chains' bits, and the three adds and the bias follow on the VALU in gru_gi's order
+// (aec_gi_map.h: the operand map and the fragment layout).  wa[t][m][r]: the lane's A operands
+// (gi_load_a), gb[t][v]: the bias of the lane's result rows, x: [16][64] in LDS, gi: [16][96] in LDS.
+typedef float f4m __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void gi_load_a(const float* W_ih, const float* b_ih, const float* b_hh, int t0, int lane,
+                                          float (&wa)[2][4][4], float (&gb)[2][4]) {
+#pragma unroll
+    for (int t = 0; t < gi_map::kTilesPerWave; ++t) {
+#pragma unroll
+        for (int m = 0; m < gi_map::kInstr; ++m) {
+            const float4 w = *reinterpret_cast<const float4*>(W_ih + gi_map::a_row(t0 + t, lane) * gi_map::kK +
+                                                              gi_map::k_of(m, 0, lane));
+            wa[t][m][0] = w.x, wa[t][m][1] = w.y, wa[t][m][2] = w.z, wa[t][m][3] = w.w;
+        }
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const int g = gi_map::d_row(t0 + t, lane, v);
+            gb[t][v] = b_ih[g] + (g < 64 ? b_hh[g] : 0.f);
+        }
+    }
+}
+__device__ __forceinline__ void gru_gi_mfma(const float (&wa)[2][4][4], const float (&gb)[2][4], const float* x,
+                                            float* gi, int t0, int lane) {
+    float4 xv[gi_map::kInstr];
+#pragma unroll
+    for (int m = 0; m < gi_map::kInstr; ++m)
+        xv[m] = *reinterpret_cast<const float4*>(x + gi_map::b_slot(lane) * gi_map::kK + gi_map::b_read(m, lane));
+    f4m acc[2][4];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[t][r] = f4m{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int m = 0; m < gi_map::kInstr; ++m) {
+        const float xr[4] = {xv[m].x, xv[m].y, xv[m].z, xv[m].w};
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                acc[t][r] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[t][m][r], xr[r], acc[t][r], 0, 0, 0);
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        float4 o;
+        o.x = gb[t][0] + ((acc[t][0][0] + acc[t][2][0]) + (acc[t][1][0] + acc[t][3][0]));
+        o.y = gb[t][1] + ((acc[t][0][1] + acc[t][2][1]) + (acc[t][1][1] + acc[t][3][1]));
+        o.z = gb[t][2] + ((acc[t][0][2] + acc[t][2][2]) + (acc[t][1][2] + acc[t][3][2]));
+        o.w = gb[t][3] + ((acc[t][0][3] + acc[t][2][3]) + (acc[t][1][3] + acc[t][3][3]));
+        *reinterpret_cast<float4*>(gi + gi_map::d_slot(lane) * gi_map::kRows + gi_map::d_row(t0 + t, lane, 0)) = o;
+    }
 }
 
 // One recurrence step on a wave: lane l owns unit j = l & 31 and the k-half

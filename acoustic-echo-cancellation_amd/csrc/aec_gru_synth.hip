@@ -56,6 +56,12 @@
 // 0.496-0.498 ms (profiles/synth_role.txt)
 #define AEC_SPEC_BUF 1
 #endif
+#ifndef AEC_GI_MFMA
+// gi = W_ih x + b on the matrix pipe (gru_gi_mfma, aec_frame.h: v_mfma_f32_16x16x4_f32, gru_gi's
+// chains bit for bit) instead of 256 v_pk_fma_f32 and 128 broadcast LDS reads per gi lane and tick
+// (0: the scalar form, A/B builds).  DESIGN §34, profiles/gi_mfma.txt
+#define AEC_GI_MFMA 1
+#endif
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -489,11 +495,19 @@ __global__ __launch_bounds__(64 * (NS + kHelperWaves), 1) void gru_synth_kernel(
     } else if (wave < NS + kGiWaves) {
         // ---------------- feats staging + input projection ----------------
         const int hl = tid - 64 * NS;                         // 0..191
+        // AEC_GI_MFMA: the wave's two row tiles of W_ih as matrix operands (32 VGPRs); otherwise a
+        // lane's whole row (64)
+#if AEC_GI_MFMA
+        const int gt0 = gi_map::kTilesPerWave * (hl >> 6);    // the wave's first row tile
+        float wa[2][4][4], gb[2][4];
+        gi_load_a(W_ih, b_ih, b_hh, gt0, lane, wa, gb);
+#else
         const int grow = hl % 96, fq = hl / 96;               // slots fq, fq + 2, ...
         float wih[64];
 #pragma unroll
         for (int k = 0; k < 64; ++k) wih[k] = W_ih[grow * 64 + k];
         const float gbias = b_ih[grow] + (grow < 64 ? b_hh[grow] : 0.f);
+#endif
         constexpr int kStU = (kCH * 32 + kGiLanes - 1) / kGiLanes;    // 3 elements per lane
         float pm[kStU], pr[kStU], pn[kStU];
         auto load_chunk = [&](int cc) {
@@ -538,11 +552,15 @@ __global__ __launch_bounds__(64 * (NS + kHelperWaves), 1) void gru_synth_kernel(
             }
             const int cg = c + 1;
             if (cg >= 0 && cg < nchmax && !(y.fmode & 2048)) {
+#if AEC_GI_MFMA
+                gru_gi_mfma(wa, gb, sX + (cg & 1) * kCH * 64, sGi + (cg & 1) * kCH * 96, gt0, lane);
+#else
 #pragma unroll 2
                 for (int i = 0; i < kCH / 2; ++i) {
                     const int q = fq + 2 * i;
                     sGi[((cg & 1) * kCH + q) * 96 + grow] = gru_gi(wih, sX + ((cg & 1) * kCH + q) * 64, gbias);
                 }
+#endif
             }
             GTICK(1);
             tick_barrier();
