@@ -31,6 +31,7 @@ EXPORTS = ('aec_weights_count', 'aec_create', 'aec_set_weights', 'aec_set_erb', 
            'aec_stream_open', 'aec_stream_reset', 'aec_stream_step', 'aec_stream_push',
            'aec_stream_open_rescue', 'aec_stream_rescue_counts',
            'aec_stream_open_stereo', 'aec_stream_step_stereo', 'aec_stream_push_stereo', 'aec_stream_state',
+           'aec_stream_open_stereo_rescue',
            'aec_delay_estimate', 'aec_delay_apply', 'aec_drift_estimate', 'aec_drift_apply',
            'aec_delay_track_open', 'aec_delay_track_reset', 'aec_delay_track_push',
            'aec_drift_track_open', 'aec_drift_track_reset', 'aec_drift_track_push',
@@ -153,6 +154,9 @@ def load():
         lib.aec_stream_push_stereo.restype = ctypes.c_int
         lib.aec_stream_state.argtypes = [P, P, P, P]
         lib.aec_stream_state.restype = ctypes.c_int
+    if LIB_PATH == _DEFAULT_LIB or hasattr(lib, 'aec_stream_open_stereo_rescue'):   # absent from an older A/B build
+        lib.aec_stream_open_stereo_rescue.argtypes = [P, ctypes.c_int32]
+        lib.aec_stream_open_stereo_rescue.restype = ctypes.c_int
     if LIB_PATH == _DEFAULT_LIB or hasattr(lib, 'aec_delay_estimate'):   # absent from an older A/B build
         lib.aec_delay_estimate.argtypes = [P, P, P, P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, P, P, P]
         lib.aec_delay_estimate.restype = ctypes.c_int
@@ -340,7 +344,7 @@ class Handle:
 
     def set_canceller_stereo_rescue(self, on, mu=0.3, gamma=0.9, ratio=0.5):
         """The stereo canceller's rescue from echo-path changes: the shadow filter over both
-        channels' histories (aec_set_canceller_stereo_rescue); batch path only."""
+        channels' histories (aec_set_canceller_stereo_rescue); its streams: stream_open_stereo_rescue."""
         check(self.lib.aec_set_canceller_stereo_rescue(self.h, int(bool(on)), float(mu), float(gamma), float(ratio)),
               self.h, 'aec_set_canceller_stereo_rescue')
         self.stereo_rescue = bool(on)
@@ -398,6 +402,10 @@ class Handle:
     def stream_open_stereo(self, B):
         """Streams of a stereo handle (aec_stream_open_stereo)."""
         check(self.lib.aec_stream_open_stereo(self.h, int(B)), self.h, 'aec_stream_open_stereo')
+
+    def stream_open_stereo_rescue(self, B):
+        """Streams of a stereo handle with the stereo rescue on (aec_stream_open_stereo_rescue)."""
+        check(self.lib.aec_stream_open_stereo_rescue(self.h, int(B)), self.h, 'aec_stream_open_stereo_rescue')
 
     def stream_step_stereo(self, mic_ptr, ref_l_ptr, ref_r_ptr, ld_mic, ld_ref, out_ptr, ld_out, stream):
         """ref_l_ptr, ref_r_ptr: the channels' rows, both ld_ref floats apart"""

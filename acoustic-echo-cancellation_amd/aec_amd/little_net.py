@@ -410,10 +410,32 @@ class Little_net(nn.Module):
         if not self.stereo:
             raise RuntimeError("this net takes one far-end channel (nlms['stereo'] is not set): stream_open opens its streams")
         if self.nlms.get('rescue'):
-            raise NotImplementedError("the stereo streams have no rescue (nlms['rescue']): the stereo rescue is the batch path's")
+            raise NotImplementedError("these streams carry no shadow filter for the stereo rescue (nlms['rescue']): "
+                                      'stream_open_stereo_rescue opens such a net\'s streams')
         self._stream_open(B, erb, device, True)
 
-    def _stream_open(self, B, erb, device, stereo):
+    def stream_open_stereo_rescue(self, B, erb, device=None):
+        """``stream_open_stereo`` for a stereo net with the rescue on
+        (``kalman_stereo_rescue_conf``; aec_stream_open_stereo_rescue): afterwards
+        ``stream_step_stereo`` / ``stream_push_stereo`` / ``stream_reset`` work with
+        their signatures unchanged and a streamed row has the batch call's bits.
+        The shadow filter costs 2 taps + 3 more rows of 256 float2 per stream behind
+        the stereo state (taps per channel; 38 KB at 8 taps) and, per hop, the
+        shadow NLMS over both channels' histories beside the main filter.
+        ``stream_rescue_counts`` returns, per stream, the (bin, frame) copies of the
+        shadow into the main filter since open / reset, bins 0 and 256 counted
+        separately: a count that moves says that stream's echo path changed.
+        RuntimeError for a net without stereo or without the rescue."""
+        if torch.is_grad_enabled() and self.training:
+            raise NotImplementedError('streaming is inference-only: use net.eval() and torch.no_grad()')
+        if not self.stereo:
+            raise RuntimeError("this net takes one far-end channel (nlms['stereo'] is not set): stream_open opens its streams")
+        if not self.nlms.get('rescue'):
+            raise RuntimeError("the stereo rescue is not on for this net (nlms['rescue'] is not set): "
+                               'stream_open_stereo opens its streams')
+        self._stream_open(B, erb, device, True, rescue=True)
+
+    def _stream_open(self, B, erb, device, stereo, rescue=False):
         device = torch.device(device or 'cuda')
         if device.type != 'cuda':
             raise RuntimeError(f'Little_net (gfx950) streams live on a HIP device, got {device}')
@@ -421,14 +443,16 @@ class Little_net(nn.Module):
             raise ValueError(f'erb must be [257, 32], got {tuple(erb.shape)}')
         h, idx = self._handle(device)
         self._sync_erb(h, idx, erb)
-        if stereo:
+        if stereo and rescue:
+            h.stream_open_stereo_rescue(B)
+        elif stereo:
             h.stream_open_stereo(B)
         elif h.rescue:
             h.stream_open_rescue(B)
         else:
             h.stream_open(B)
         self._stream = (h, torch.device('cuda', idx), int(B))
-        self._stream_rescue = bool(h.rescue)
+        self._stream_rescue = bool(h.rescue) or bool(stereo and rescue)
         self._stream_stereo = bool(stereo)
 
     def _stream_state(self, stereo=False):

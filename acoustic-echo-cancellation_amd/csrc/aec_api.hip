@@ -133,7 +133,8 @@ struct aec_handle {
     float* d_state = nullptr;
     int32_t stream_B = 0;
     int64_t stream_stride = 0;
-    bool stream_rescue = false;  // the state is a rescue stream's (aec_stream_open_rescue): shadow rows, copy counter
+    bool stream_rescue = false;  // the state is a rescue stream's (aec_stream_open_rescue; with stream_stereo:
+                                 // aec_stream_open_stereo_rescue): shadow rows, copy counter
     bool stream_stereo = false;  // the state is a stereo stream's (aec_stream_open_stereo): stereo_stream_rows' layout
     // streaming delay tracker (aec_delay_track_*): per-stream state [track_B][track_stride]
     float* d_track = nullptr;
@@ -294,6 +295,7 @@ const char* aec_build_info(void) {
                                     " canceller_stereo=kalman:1-" + std::to_string(aec::kStereoMaxTaps) +
                                     " stream_stereo=kalman:1-" + std::to_string(aec::kStereoMaxTaps) +
                                     " canceller_stereo_rescue=kalman:1-" + std::to_string(aec::kStereoRescueMaxTaps) +
+                                    " stream_stereo_rescue=kalman:1-" + std::to_string(aec::kStereoRescueMaxTaps) +
                                     " mode_knobs=" + aec::kModeKnobs;
     return info.c_str();
 }
@@ -984,10 +986,20 @@ aec_status aec_stream_open_rescue(aec_handle* h, int32_t B) {
 aec_status aec_stream_open_stereo(aec_handle* h, int32_t B) {
     if (!h) return AEC_ERR_INVALID_ARG;
     if (!h->stereo) return fail(h, AEC_ERR_INVALID_ARG, "the stereo far end is not on for this handle (aec_set_canceller_stereo)");
-    if (h->srescue.on) return fail(h, AEC_ERR_UNSUPPORTED, "the stereo streams have no rescue: switch it off first (aec_set_canceller_stereo_rescue)");
+    if (h->srescue.on) return fail(h, AEC_ERR_UNSUPPORTED, "this state has no rows for the stereo rescue's shadow filter: aec_stream_open_stereo_rescue opens such a handle's streams");
     if (B < 1) return fail(h, AEC_ERR_INVALID_ARG, "stream count must be >= 1");
     AEC_ON_DEVICE(h);
     return stream_open_state(h, B, false, true);
+}
+
+// The streams of a stereo handle with the stereo rescue on: the stereo state with
+// the shadow's rows behind it and the rescue streams' counter
+aec_status aec_stream_open_stereo_rescue(aec_handle* h, int32_t B) {
+    if (!h) return AEC_ERR_INVALID_ARG;
+    const std::string why = check_stream_open_stereo_rescue(h->stereo != 0, h->srescue.on != 0, B, h->d_state != nullptr);
+    if (!why.empty()) return fail(h, AEC_ERR_INVALID_ARG, why);
+    AEC_ON_DEVICE(h);
+    return stream_open_state(h, B, true, true);
 }
 
 aec_status aec_stream_state(aec_handle* h, float** state, int64_t* stride, int32_t* B) {
@@ -1002,7 +1014,7 @@ aec_status aec_stream_state(aec_handle* h, float** state, int64_t* stride, int32
 
 aec_status aec_stream_rescue_counts(aec_handle* h, int64_t* counts, void* stream) {
     if (!h) return AEC_ERR_INVALID_ARG;
-    if (!h->d_state || !h->stream_rescue) return fail(h, AEC_ERR_INVALID_ARG, "aec_stream_open_rescue first");
+    if (!h->d_state || !h->stream_rescue) return fail(h, AEC_ERR_INVALID_ARG, "aec_stream_open_rescue (or aec_stream_open_stereo_rescue) first");
     if (!counts) return fail(h, AEC_ERR_INVALID_ARG, "null counts");
     AEC_ON_DEVICE(h);
     HIP_TRY(h, launch_stream_rescue_counts(h->d_state, h->stream_stride, h->stream_B, counts, reinterpret_cast<hipStream_t>(stream)));
@@ -1080,7 +1092,7 @@ static aec_status stream_stereo_call(aec_handle* h, const float* mic, const floa
                                      int64_t ld_ref, float* out, int64_t ld_out, const int32_t* hops, int32_t max_hops,
                                      bool step, void* stream) {
     if (!h) return AEC_ERR_INVALID_ARG;
-    if (!h->d_state || !h->stream_stereo) return fail(h, AEC_ERR_INVALID_ARG, "aec_stream_open_stereo first");
+    if (!h->d_state || !h->stream_stereo) return fail(h, AEC_ERR_INVALID_ARG, "aec_stream_open_stereo (or aec_stream_open_stereo_rescue) first");
     if (!h->have_w || !h->have_erb) return fail(h, AEC_ERR_INVALID_ARG, "weights / erb not set");
     if (!mic || !ref_l || !ref_r || !out) return fail(h, AEC_ERR_INVALID_ARG, "null mic / ref_l / ref_r / out");
     Check c = check_stream_push(max_hops, ld_mic, ld_out);
@@ -1096,8 +1108,15 @@ static aec_status stream_stereo_call(aec_handle* h, const float* mic, const floa
     a.p.s.c = h->canceller();
     a.p.hops = hops; a.p.max_hops = max_hops;
     // one hop for every stream is the step: the same result from the kernel without the hop loop
-    if (step || (!hops && max_hops == 1)) HIP_TRY(h, launch_stream_step_stereo(a, h->stream_B, reinterpret_cast<hipStream_t>(stream)));
-    else HIP_TRY(h, launch_stream_push_stereo(a, h->stream_B, reinterpret_cast<hipStream_t>(stream)));
+    const bool one = step || (!hops && max_hops == 1);
+    hipStream_t hs = reinterpret_cast<hipStream_t>(stream);
+    if (h->stream_rescue) {                // aec_stream_open_stereo_rescue's state: the kernels of aec_stream_stereo_rescue.hip
+        if (one) HIP_TRY(h, launch_stream_step_stereo_rescue(a, h->srescue, h->stream_B, hs));
+        else HIP_TRY(h, launch_stream_push_stereo_rescue(a, h->srescue, h->stream_B, hs));
+        return AEC_OK;
+    }
+    if (one) HIP_TRY(h, launch_stream_step_stereo(a, h->stream_B, hs));
+    else HIP_TRY(h, launch_stream_push_stereo(a, h->stream_B, hs));
     return AEC_OK;
 }
 

@@ -219,6 +219,23 @@ constexpr StereoStreamRows stereo_stream_rows(int taps) {
     return s;
 }
 
+// A stereo stream with the rescue (aec_stream_open_stereo_rescue), `taps` per
+// channel: the stereo stream's block above, rows and meaning unchanged (stereo_stream_rows(taps)),
+// with the shadow's 2 taps + 3 rows behind it as a rescue stream appends them: Ws[0 .. taps) the
+// left channel's, Ws[taps .. 2 taps) the right's, Pn, qe, qs.
+constexpr CancellerRows stereo_rescue_stream_rows(int taps) { return canceller_rows(2 * taps, true, true); }
+
+// aec_stream_open_stereo_rescue's rule: "" or why the call is refused (AEC_ERR_INVALID_ARG).
+// stereo / stereo_rescue: the handle's settings; an open state of any kind is replaced, as by the
+// other open calls, so stream_open does not enter.
+inline std::string check_stream_open_stereo_rescue(bool stereo, bool stereo_rescue, int B, bool stream_open) {
+    (void)stream_open;
+    if (!stereo || !stereo_rescue)
+        return "the stereo rescue is not on for this handle (aec_set_canceller_stereo, then aec_set_canceller_stereo_rescue)";
+    if (B < 1) return "stream count must be >= 1";
+    return "";
+}
+
 // --------------------------------------------------------------------------
 // dispatch
 // --------------------------------------------------------------------------

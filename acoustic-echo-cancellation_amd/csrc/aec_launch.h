@@ -150,6 +150,12 @@ struct StreamStereoArgs {
     int64_t ld_ref;
 };
 static_assert(std::is_trivially_copyable<StreamStereoArgs>::value, "kernel argument blocks");
+// ... and of the stereo streams with the rescue (aec_stream_stereo_rescue.hip): the
+// stereo block, unchanged, with the rescue's parameters behind it, as StreamStepRescueArgs
+struct StreamStereoRescueArgs : StreamStereoArgs {
+    CancellerRescue r;
+};
+static_assert(std::is_trivially_copyable<StreamStereoRescueArgs>::value, "kernel argument blocks");
 
 // dynamic LDS bytes (must match the carve in the kernels)
 inline size_t analysis_smem_bytes(int sched_len) {
@@ -245,6 +251,11 @@ hipError_t launch_stream_rescue_counts(const float* state, int64_t stride, int B
 // a.p.max_hops: one hop for every stream.
 hipError_t launch_stream_step_stereo(const StreamStereoArgs& a, int B, hipStream_t st);
 hipError_t launch_stream_push_stereo(const StreamStereoArgs& a, int B, hipStream_t st);
+// ... with the stereo canceller's rescue, 1..kStereoRescueMaxTaps taps per channel
+// (aec_stream_stereo_rescue.hip): the same phases over a state with the shadow's rows behind the
+// stereo block (stereo_rescue_stream_rows) and the copy counter of the rescue streams (kStCopies)
+hipError_t launch_stream_step_stereo_rescue(const StreamStereoArgs& a, const CancellerRescue& r, int B, hipStream_t st);
+hipError_t launch_stream_push_stereo_rescue(const StreamStereoArgs& a, const CancellerRescue& r, int B, hipStream_t st);
 // K3+K4 fused (aec_gru_synth.hip): GRU + head + synthesis of the NLMS error spectrum, one stream per
 // block or two (Plan::gru_one, aec_host.h)
 hipError_t launch_gru_synth(const GruArgs& g, const SynthArgs& y, int B, bool one_per_block, hipStream_t st);

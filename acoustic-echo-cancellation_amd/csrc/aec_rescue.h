@@ -135,6 +135,21 @@ __device__ __forceinline__ void bin_store(const RescueBin<TAPS>& rb, float2* nst
     shadow_store(rb, nst, k);
 }
 
+// One lane's stereo canceller with the rescue, L taps per channel: RescueBin<2L>
+// behind StereoBin's one history write (aec_frame.h: R_R[t] into slot L - 1 before the main
+// filter's shift carries it into slot L).  The shadow reads the operands that shift leaves, so its
+// two partial chains over [0, L) and [L, 2L) are the two channels', the sums RescueHalf<2L> forms
+// on two lanes in aec_stereo_rescue.hip.
+template <int L>
+struct StereoRescueBin : RescueBin<2 * L> {
+    static constexpr int kChanTaps = L;
+    __device__ __forceinline__ float2 step(float2 d, float2 rl, float2 rr, float a, float beta, float delta, float p0,
+                                           float mu, float gamma, float ratio, bool& cx, bool& cy) {
+        this->k.hist(L - 1, rr);
+        return RescueBin<2 * L>::step(d, rl, a, beta, delta, p0, mu, gamma, ratio, cx, cy);
+    }
+};
+
 // This wave's copies of one frame, for a rescue stream's counter: the bins whose x half copied (a
 // complex lane decides the same in both halves), and on the slot-0 lane, which runs the real bins
 // 0 and 256, bin 256's own decision.  One ballot and one popcount; the result is wave-uniform

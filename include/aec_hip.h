@@ -162,8 +162,10 @@ aec_status aec_set_canceller_stereo(aec_handle* h, int32_t on);
  * serves its copy decisions.  A setting of its own: aec_set_canceller_rescue and
  * aec_set_canceller_stereo keep refusing each other as stated above.  on = 0 switches it
  * off (mu, gamma, ratio are then ignored), as does every later successful
- * aec_set_canceller and aec_set_canceller_stereo (on or off).  Batch path only:
- * aec_stream_open_stereo on a handle with it on returns AEC_ERR_UNSUPPORTED.
+ * aec_set_canceller and aec_set_canceller_stereo (on or off).  Streaming: a handle
+ * with it on opens its streams with aec_stream_open_stereo_rescue (below), whose
+ * state carries the shadow; aec_stream_open_stereo on such a handle returns
+ * AEC_ERR_UNSUPPORTED.
  * AEC_ERR_INVALID_ARG: not a Kalman handle with stereo on, a streaming state is open,
  * or (on != 0) mu negative or not finite, gamma outside [0, 1), ratio negative or not
  * finite.  AEC_ERR_UNSUPPORTED: nlms_taps > 8. */
@@ -336,8 +338,23 @@ aec_status aec_stream_rescue_counts(aec_handle* h, int64_t* counts, void* stream
  * of aec_stream_push; aec_stream_step / aec_stream_push on an open stereo state
  * (the text names these entries); aec_stream_rescue_counts on a stereo state.
  * AEC_ERR_UNSUPPORTED: aec_stream_open_stereo on a handle with the stereo rescue on
- * (aec_set_canceller_stereo_rescue): the stereo streams have no rescue. */
+ * (aec_set_canceller_stereo_rescue): this state has no rows for the shadow, and
+ * aec_stream_open_stereo_rescue opens such a handle's streams.
+ *
+ * aec_stream_open_stereo_rescue(h, B): the streams of a stereo handle
+ * with the stereo rescue on.  The state is aec_stream_open_stereo's, rows and meaning
+ * unchanged, with the shadow filter behind it (Ws, Pn, qe, qs: 2 nlms_taps + 3 rows of
+ * 256 float2, all zero at stream start) and the copy counter of
+ * aec_stream_open_rescue's states.  Afterwards aec_stream_step_stereo,
+ * aec_stream_push_stereo (packets, per-stream counts, the untouched 0-hop stream) and
+ * aec_stream_reset work on it as on a plain stereo state, step and push mix, and
+ * aec_stream_rescue_counts returns the counts; a hop runs the batch recursion's bin, so
+ * a streamed utterance reproduces aec_process_stereo's row on the same handle bit for
+ * bit.  aec_stream_step / aec_stream_push refuse as on any stereo state, the setters as
+ * for any open stream.  AEC_ERR_INVALID_ARG: the handle is not stereo, its stereo
+ * rescue is not on, or B < 1. */
 aec_status aec_stream_open_stereo(aec_handle* h, int32_t B);
+aec_status aec_stream_open_stereo_rescue(aec_handle* h, int32_t B);
 aec_status aec_stream_step_stereo(aec_handle* h, const float* mic, const float* ref_l, const float* ref_r,
                                   int64_t ld_mic, int64_t ld_ref, float* out, int64_t ld_out, void* stream);
 aec_status aec_stream_push_stereo(aec_handle* h, const float* mic, const float* ref_l, const float* ref_r,
